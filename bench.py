@@ -12,6 +12,10 @@ candidate features -> per-cloud chamfer graph + one propagation hop -> FPS selec
 Metric = input tile points through that whole pipe per second (BASELINE.json).  Tiles shard across GPUs with no
 data-path collective until the candidates' propagated features are all-gathered before the (replicated) global
 FPS: weak scaling.
+
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step
+= the timed region over the steps, ...).  --full adds the legs beside the headline (rooflines, one AL round at the reference's scale,
+the CPU baseline, the N > 1 fixed-batch reading); --dump-outputs DIR writes what the last timed step computed, for comparing builds.
 """
 import argparse
 import json
@@ -75,6 +79,29 @@ def launch_ranks(n):
     return subprocess.run(cmd, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")).returncode
 
 
+DUMP_ROWS = 131072                # network rows kept by --dump-outputs (of 16 x 40960 per batch): a fixed, seeded sample
+
+
+def dump_outputs(d, last, h):
+    """What a caller of the timed path receives from its last step, as float32 / float64 .npy files in d: the step's return value (the picks
+    into the candidate list, the candidates as (cloud, region) pairs), the picks as (room id, region in room), and the network's per-point
+    outputs of that batch (class probabilities, the 32 features, the uncertainty) at the same seeded sample of rows in every run."""
+    os.makedirs(d, exist_ok=True)
+    sel, unl = last
+    cand = unl.tolist() if hasattr(unl, "tolist") else list(unl)
+    rows = h.B * h.cfg.num_points
+    pick = np.sort(np.random.default_rng(0).choice(rows, DUMP_ROWS, replace=False)) if rows > DUMP_ROWS else np.arange(rows)
+    out = {"selected": np.asarray(sel, np.float64),
+           "candidates": np.asarray(cand, np.float64).reshape(-1, 2),
+           "selected_regions": np.asarray(h.selected, np.float64).reshape(-1, 2),
+           "probs": h.probs.to_host()[pick].astype(np.float32),
+           "features": h.f32.to_host()[pick].astype(np.float32),
+           "uncertainty": h.unc.to_host().reshape(-1)[pick].astype(np.float32),
+           "sample_rows": pick.astype(np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -105,7 +132,16 @@ def main():
     ap.add_argument("--emu", action="store_true",
                     help="TEST ONLY (tests/test_bench_launch.py): CPU logic build of the kernels + gloo, a tiny workload; exercises the launcher and the "
                          "N > 1 control flow on a box without GPUs, measures nothing")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: the N > 1 fixed-batch reading, the per-kernel / per-stage rooflines (--stages), one AL round "
+                         "at the reference's scale (--no-al-round) and the CPU baseline (--no-cpu-baseline); without it the run sets up, warms up, times "
+                         "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64; rank 0's batch): the "
+                         "selection, the candidate list, the picked regions, and a fixed sample of the network's rows")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and not args.emu and not os.environ.get("SSDR_BENCH_SKIP_DEVICE_COUNT"):
         have = count_gpus()
@@ -218,12 +254,15 @@ def main():
     barrier()
     t0 = time.perf_counter()
     if pipe is not None:
-        pipe.run(args.steps, gather)
+        last = pipe.run(args.steps, gather)
     else:
         for _ in range(args.steps):
-            hp.step(gather)
+            last = hp.step(gather)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # the buffer set of the last timed batch: no later batch was issued into it (the legs of --full come after this)
+        dump_outputs(args.dump_outputs, last, pipe.hp[(args.steps - 1) % pipe.slots] if pipe is not None else hp)
     if use_dist:
         import torch
         t = torch.tensor([dt], device="cpu" if args.emu else "cuda", dtype=torch.float64)
@@ -237,7 +276,7 @@ def main():
     # global farthest-point chain is N x the picks over N x the rows: N^2); the reference's own reading is ONE batch_size per round whatever the
     # number of clouds (ssdr_main_S3DIS2.py:134) — the chain then stays what one rank runs.  Same path, same timed region, the other batch size.
     fixed_batch = None
-    if use_dist and args.global_batch == 0 and (world > 1 or os.environ.get("SSDR_BENCH_FORCE_DIST")):
+    if args.full and use_dist and args.global_batch == 0 and (world > 1 or os.environ.get("SSDR_BENCH_FORCE_DIST")):
         K_fixed = hp.select_per_tile * tiles_per_gpu
         hps = [hp] + (list(pipe.hp) if pipe is not None else [])
 
@@ -269,7 +308,7 @@ def main():
                        "note": "the reference's reading: sampling()'s batch_size is ONE number for the round (here what one rank's 16 tiles select), the replicated chain does not grow with N"}
         set_batch(None)
 
-    # ---- roofline leg (untimed): per-launch HIP-event timing of the instrumented kernels ------------------
+    # ---- roofline leg (--full, untimed): per-launch HIP-event timing of the instrumented kernels ------------------
     L = _lib.lib()
 
     def prof_rows(run):
@@ -289,12 +328,12 @@ def main():
     mfma_peak = PEAK_F32_MFMA_TFLOPS if args.precision == "f32" else PEAK_BF16_MFMA_TFLOPS
     mfma_insn = "v_mfma_f32_16x16x4_f32" if args.precision == "f32" else ("v_mfma_f32_16x16x32_bf16 (LocSE K = 10 and the d = 16 level on v_mfma_f32_16x16x4_f32)" if args.tiles16 else "v_mfma_f32_32x32x16_bf16 (every level; softmax over the neighbours inside the lane)")
     # (a) the way the timed region ran (every rank takes part because of the exchanges) ...
-    timed_rows = [] if args.emu else prof_rows((lambda: (pipe.run(NPROF, gather), pipe.finish())) if pipe is not None else (lambda: [hp.step(gather) for _ in range(NPROF)]))
+    timed_rows = [] if args.emu or not args.full else prof_rows((lambda: (pipe.run(NPROF, gather), pipe.finish())) if pipe is not None else (lambda: [hp.step(gather) for _ in range(NPROF)]))
     roofline = None
     stage_ms = None
     stage_roofline = None
     whole_step = None
-    if rank == 0 and not args.emu:
+    if rank == 0 and not args.emu and args.full:
         # (b) ... and strictly sequential on rank 0: the kernel with the GPU to itself.  (b) is the roofline figure: it is
         # the kernel's own duration (rocprofv3's per-dispatch duration agrees with it, profiles/rNN_bench_seq_kernel_stats.csv),
         # whereas with several batches in flight an event pair on one stream also spans the time the dispatch waits
@@ -418,12 +457,12 @@ def main():
             if args.stages:
                 print("stages(ms, sequential):", stage_ms, file=sys.stderr)
 
-    # ---- one AL round at the reference's own scale (rank 0, N = 1; not the headline): inference over ALL rooms, then ONE selection ----
+    # ---- one AL round at the reference's own scale (--full, rank 0, N = 1; not the headline): inference over ALL rooms, then ONE selection ----
     # The headline step selects per 16-tile batch (the reference's picks-per-tile ratio), which under-represents the quadratic term of the
     # farthest-point chain 17-fold: the reference runs the network over all 272 rooms and then ONE GCN_FPS_sampling of batch_size = 10 000
     # over 2 x 10 000 candidates + the labelled rows (ssdr_main_S3DIS2.py:134, sampler2.py:736-781).  pipeline.ALRound is that round.
     al_round = None
-    if rank == 0 and world == 1 and not args.emu and not args.no_al_round:
+    if args.full and rank == 0 and world == 1 and not args.emu and not args.no_al_round:
         try:
             ar = pipeline.ALRound(weights, rooms, args.al_batches, Cfg, batch_size=args.al_batch_size, precision=args.precision, selector=args.selector, tiles32=not args.tiles16)
             ar.run()                                   # untimed: grows the scratch buffers
@@ -455,9 +494,9 @@ def main():
             al_round = {"error": "%s: %s" % (type(e).__name__, e)}
             L.ssdr_prof_enable(0)
 
-    # ---- CPU baseline leg (rank 0, N = 1 only): the oracle pipeline on ONE room/tile of the same workload ----
+    # ---- CPU baseline leg (--full, rank 0, N = 1 only): the oracle pipeline on ONE room/tile of the same workload ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import pipeline_np
         cores = os.cpu_count() or 1
         ns = 4
@@ -491,7 +530,7 @@ def main():
 
     if rank == 0:
         assert world == args.gpus or os.environ.get("SSDR_BENCH_FORCE_DIST"), "n_gpus must be what --gpus asked for"
-        out = {"metric": METRIC, "value": round(value, 3), "unit": "Mpoints/s", "n_gpus": world, "ranks_seen": ranks_seen, "steps": args.steps, "warmup": args.warmup,
+        out = {"metric": METRIC, "value": round(value, 3), "unit": "Mpoints/s", "n_gpus": world, "ranks_seen": ranks_seen, "steps": args.steps, "warmup": args.warmup, "full": args.full,
                "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                "dtype": DTYPE[args.precision], "data": "synthetic" if not args.emu else "synthetic (TEST MODE: CPU logic build, tiny workload - not a measurement)",
                "config": {"workload": "S3DIS-like rooms (synthetic, Area_5 seeds), %d rooms/tiles of 40960 points per GPU per step: grid-subsample "

@@ -7,6 +7,6 @@ cd $GRAFT_REPO_ROOT
 for r in 1 2 3; do
   for lib in "$@"; do
     echo -n "$lib: "
-    SSDR_AL_LIBRARY=$PWD/$lib timeout 120 python3 bench.py --no-cpu-baseline $BENCH_EXTRA 2>/dev/null | grep '^{"metric"' | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['stage_ms'])"
+    SSDR_AL_LIBRARY=$PWD/$lib timeout 120 python3 bench.py --full --no-cpu-baseline $BENCH_EXTRA 2>/dev/null | grep '^{"metric"' | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['stage_ms'])"
   done
 done

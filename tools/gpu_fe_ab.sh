@@ -14,5 +14,5 @@ done
 for lib in "abtmp/lib_w4.so 1" "abtmp/lib_w4.so 0" "abtmp/lib_w5.so 0" "abtmp/lib_w6.so 0" "abtmp/lib_w4.so 1" "abtmp/lib_w4.so 0" "abtmp/lib_w5.so 0" "abtmp/lib_w6.so 0"; do
   set -- $lib
   echo -n "bench $1 IMAGE=$2: "
-  SSDR_AL_LIBRARY=$PWD/$1 SSDR_FE_IMAGE=$2 timeout 120 python3 bench.py --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['stage_ms']['subsample+tile'], d['roofline']['others']['fe_reduce']['ms_per_step'])"
+  SSDR_AL_LIBRARY=$PWD/$1 SSDR_FE_IMAGE=$2 timeout 120 python3 bench.py --full --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['stage_ms']['subsample+tile'], d['roofline']['others']['fe_reduce']['ms_per_step'])"
 done

@@ -10,5 +10,5 @@ for r in 1 2; do
 done
 for lib in abtmp/lib_nt256.so abtmp/lib_nt128.so abtmp/lib_nt256.so abtmp/lib_nt128.so; do
   echo -n "bench $lib: "
-  SSDR_AL_LIBRARY=$PWD/$lib SSDR_FE_WGS=$([ $lib = abtmp/lib_nt128.so ] && echo 16 || echo 8) timeout 120 python3 bench.py --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['stage_ms']['subsample+tile'], d['roofline']['others']['fe_reduce']['ms_per_step'])"
+  SSDR_AL_LIBRARY=$PWD/$lib SSDR_FE_WGS=$([ $lib = abtmp/lib_nt128.so ] && echo 16 || echo 8) timeout 120 python3 bench.py --full --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['stage_ms']['subsample+tile'], d['roofline']['others']['fe_reduce']['ms_per_step'])"
 done

@@ -4,5 +4,5 @@ cd $GRAFT_REPO_ROOT
 for r in 1 2 3; do for lib in "$@"; do echo -n "$lib: "; SSDR_AL_LIBRARY=$PWD/$lib timeout 120 python3 tools/fe_bench.py 30 0,0 2>&1 | tail -1; done; done
 for r in 1 2; do for lib in "$@"; do
   echo -n "bench $lib: "
-  SSDR_AL_LIBRARY=$PWD/$lib timeout 120 python3 bench.py --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); o=d['roofline']['others']; print(d['value'], d['ms_per_step'], d['stage_ms']['subsample+tile'], {k: o[k]['ms_per_step'] for k in o if k.startswith('fe_') or k.startswith('tile')})"
+  SSDR_AL_LIBRARY=$PWD/$lib timeout 120 python3 bench.py --full --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); o=d['roofline']['others']; print(d['value'], d['ms_per_step'], d['stage_ms']['subsample+tile'], {k: o[k]['ms_per_step'] for k in o if k.startswith('fe_') or k.startswith('tile')})"
 done; done

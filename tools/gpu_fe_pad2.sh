@@ -11,5 +11,5 @@ PY
 done
 for r in 1 2 3; do for pad in 0 8000 11000; do
   echo -n "bench pad $pad: "
-  SSDR_FE_PADLDS=$pad timeout 120 python3 bench.py --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); o=d['roofline']['others']; print(d['value'], d['ms_per_step'], d['stage_ms']['subsample+tile'], o['fe_reduce']['ms_per_step'])"
+  SSDR_FE_PADLDS=$pad timeout 120 python3 bench.py --full --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); o=d['roofline']['others']; print(d['value'], d['ms_per_step'], d['stage_ms']['subsample+tile'], o['fe_reduce']['ms_per_step'])"
 done; done

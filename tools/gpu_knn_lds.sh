@@ -8,7 +8,7 @@ for v in 0 1; do
   export SSDR_KNN_LDS=$v
   echo "== SSDR_KNN_LDS=$v"
   timeout 200 python -m pytest tests/test_knn.py -m gpu -x -q 2>&1 | tail -1
-  timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kts$v -o kts -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-pipeline > $OUT/bench_$v.json 2> $OUT/kts$v.err
+  timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kts$v -o kts -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-pipeline > $OUT/bench_$v.json 2> $OUT/kts$v.err
   python3 - <<PY
 import csv, json
 rows=list(csv.DictReader(open("$OUT/kts$v/kts_kernel_stats.csv")))

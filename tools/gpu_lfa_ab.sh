@@ -9,7 +9,7 @@ i=0
 for v in "$@"; do
   i=$((i+1))
   env $v python3 -c "print('== $v')"
-  ( export $v; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kts$i -o kts -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-pipeline $BENCH_EXTRA > $OUT/bench_seq_$i.json 2> $OUT/kts$i.err )
+  ( export $v; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kts$i -o kts -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-pipeline $BENCH_EXTRA > $OUT/bench_seq_$i.json 2> $OUT/kts$i.err )
   python3 - <<PY
 import csv, json
 rows=list(csv.DictReader(open("$OUT/kts$i/kts_kernel_stats.csv")))

@@ -5,7 +5,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/net
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 python -m pytest tests/test_randla.py -m gpu -x -q -s 2>&1 | tail -8
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kts -o kts -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-pipeline --precision $P > $OUT/bench_seq.json 2> $OUT/kts.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kts -o kts -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-pipeline --precision $P > $OUT/bench_seq.json 2> $OUT/kts.err
 python - <<PY
 import csv
 rows=list(csv.DictReader(open("$OUT/kts/kts_kernel_stats.csv")))

@@ -4,7 +4,7 @@ P=${1:-bf16x3}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/netseq
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --output-format csv -d $OUT/kt -o kt -- python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-pipeline --precision $P > $OUT/bench.json 2> $OUT/kt.err
+rocprofv3 --kernel-trace --output-format csv -d $OUT/kt -o kt -- python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-pipeline --precision $P > $OUT/bench.json 2> $OUT/kt.err
 python - <<PY > $OUT/netseq_$P.txt
 import csv, statistics
 rows=list(csv.DictReader(open("$OUT/kt/kt_kernel_trace.csv")))

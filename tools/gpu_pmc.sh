@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 i=0
 for C in "$@"; do
   i=$((i+1))
-  rocprofv3 --pmc $C --output-format csv -d $OUT/p$i -o p -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-pipeline --precision $P > /dev/null 2> $OUT/p$i.err
+  rocprofv3 --pmc $C --output-format csv -d $OUT/p$i -o p -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-pipeline --precision $P > /dev/null 2> $OUT/p$i.err
   cp $OUT/p$i/p_counter_collection.csv $OUT/pass$i.csv; rm -rf $OUT/p$i
 done
 ls -la $OUT

@@ -11,7 +11,7 @@ for C in "SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_I
          "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum TCP_TCP_TA_DATA_STALL_CYCLES_sum" \
          "TCC_HIT_sum TCC_MISS_sum TCC_READ_sum TD_TD_BUSY_sum"; do
   i=$((i+1))
-  timeout 170 rocprofv3 --pmc $C --kernel-include-regex "$RX" --output-format csv -d $OUT/p$i -o p -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-pipeline > /dev/null 2> $OUT/p$i.err
+  timeout 170 rocprofv3 --pmc $C --kernel-include-regex "$RX" --output-format csv -d $OUT/p$i -o p -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-pipeline > /dev/null 2> $OUT/p$i.err
   cp $OUT/p$i/p_counter_collection.csv $OUT/pass$i.csv 2>/dev/null; rm -rf $OUT/p$i
 done
 python3 - <<PY

@@ -5,7 +5,7 @@ mkdir -p $OUT; : > $OUT/map.txt
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 one() {
   rm -rf $OUT/kt
-  rocprofv3 --kernel-trace --output-format csv -d $OUT/kt -o kt -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-al-round > $OUT/bench.json 2> $OUT/kt.err
+  rocprofv3 --kernel-trace --output-format csv -d $OUT/kt -o kt -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-al-round > $OUT/bench.json 2> $OUT/kt.err
   python - >> $OUT/map.txt <<PY
 import csv, json, collections, os
 rows=list(csv.DictReader(open("$OUT/kt/kt_kernel_trace.csv")))

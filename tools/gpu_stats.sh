@@ -5,7 +5,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/stats
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 if [ -n "$3" ]; then timeout 900 python -m pytest $3 -m gpu -x -q 2>&1 | tail -3; fi
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kts -o kts -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-pipeline --precision $P > $OUT/bench_seq.json 2> $OUT/kts.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kts -o kts -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-pipeline --precision $P > $OUT/bench_seq.json 2> $OUT/kts.err
 python - <<PY
 import csv, json
 d=json.load(open("$OUT/bench_seq.json")); print("sequential:", d["value"], "Mpts/s", d["ms_per_step"], "ms/step", d["stage_ms"])

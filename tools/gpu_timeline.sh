@@ -4,7 +4,7 @@ P=${1:-bf16x3}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/timeline
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --output-format csv -d $OUT/kt -o kt -- python3 bench.py --steps 30 --warmup 3 --no-cpu-baseline --precision $P > $OUT/bench.json 2> $OUT/kt.err
+rocprofv3 --kernel-trace --output-format csv -d $OUT/kt -o kt -- python3 bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --precision $P > $OUT/bench.json 2> $OUT/kt.err
 python - <<PY
 import csv, json, collections
 print(json.load(open("$OUT/bench.json"))["value"])

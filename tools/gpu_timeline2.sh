@@ -3,7 +3,7 @@
 OUT=$GRAFT_REPO_ROOT/gpurun_out/timeline2
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --output-format csv -d $OUT/kt -o kt -- python3 bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-al-round > $OUT/bench.json 2> $OUT/kt.err
+rocprofv3 --kernel-trace --output-format csv -d $OUT/kt -o kt -- python3 bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-al-round > $OUT/bench.json 2> $OUT/kt.err
 python - > $OUT/timeline.txt <<PY
 import csv, json, collections
 print(json.load(open("$OUT/bench.json"))["value"])

@@ -68,7 +68,7 @@ try:      # optional third pass: SQ_VALU_MFMA_BUSY_CYCLES / SQ_BUSY_CYCLES per k
     MFMA = {k: v for k, v in busy.items() if v[0] > 0}
 except FileNotFoundError:
     pass
-out = {"commit": commit, "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `bench.py --steps 1 --warmup 0 --no-cpu-baseline "
+out = {"commit": commit, "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `bench.py --full --steps 1 --warmup 0 --no-cpu-baseline "
                  "--no-pipeline` (tools/collect_profiles.sh); counters are KB; FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 tallies "
                  "128-B requests as 64 B), which over-counts kernels whose reads are mostly 64-B gathers", "kernels": {}}
 for k in sorted(set(f) | set(w), key=lambda k: -(2 * f[k][1] + w[k][1])):
