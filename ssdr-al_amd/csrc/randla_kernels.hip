@@ -749,7 +749,8 @@ int launch_dense(const DenseArgs& a, hipStream_t s) {
     const bool rows_form = a.M >= 1024 && ((uintptr_t)a.y & 15) == 0 && ((uintptr_t)a.x2 & 15) == 0 && (a.k1 % 4 != 0 || ((uintptr_t)a.x1 & 15) == 0) && a.k2 == 0 && a.N == 8 &&
                            (a.k1 == 6 || a.k1 == 8 || a.k1 == 16);
     // (the thin one-row-per-lane layers stream their rows on fp32 FMAs: charged by the bytes they move, 4 (k + N) per row)
-    ProfScope prof(rows_form ? "dense_rows_kernel" : "dense_kernel", s, rows_form ? 4.0 * (double)a.M * (double)(a.k1 + a.N) : 2.0 * (double)a.M * (double)(a.k1 + a.k2) * (double)a.N,
+    // (the scalar-load form has a name of its own: it only runs for shapes outside the reference's configuration, in_dim != 6 or fewer than 1024 rows)
+    ProfScope prof(rows_form ? "dense_rows_kernel" : vec ? "dense_kernel" : "dense_kernel<false>", s, rows_form ? 4.0 * (double)a.M * (double)(a.k1 + a.N) : 2.0 * (double)a.M * (double)(a.k1 + a.k2) * (double)a.N,
                    rows_form ? 0.0 : 2.0 * (double)a.M * (double)(a.k1 + a.k2) * (double)a.N);
     if (rows_form) {
         const dim3 g((unsigned)((a.M + 255) / 256));
@@ -843,6 +844,7 @@ int launch_tail(const float* x, const float* W1, const float* b1, const float* W
 int launch_head(const float* x, const float* W, const float* b, int M, int C, float* probs, hipStream_t s) {
     if (M <= 0) return SSDR_OK;
     if (C > 32) { set_error("num_classes=%d > 32 is not supported", C); return SSDR_ERR_UNSUPPORTED; }
+    ProfScope prof("head_kernel", s, (double)M * 4.0 * (32 + C));
     dim3 grid((unsigned)std::max(1, std::min((M + 255) / 256, 4096)));
     hipLaunchKernelGGL(head_kernel, grid, dim3(256), 0, s, x, W, b, M, C, probs);
     SSDR_HIP(hipGetLastError());

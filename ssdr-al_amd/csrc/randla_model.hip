@@ -177,6 +177,7 @@ int ssdr_randla_create(int num_layers, const int32_t* d_out, int k_n, int num_cl
     if (!handle || !d_out || num_layers < 1 || num_layers > 8) { set_error("randla_create: bad arguments"); return SSDR_ERR_INVALID; }
     if (k_n != 16) { set_error("randla: k_n=%d is not supported (16)", k_n); return SSDR_ERR_UNSUPPORTED; }
     if (num_classes < 1 || num_classes > 32) { set_error("randla: num_classes must be in [1,32]"); return SSDR_ERR_UNSUPPORTED; }
+    if (in_dim < 1) { set_error("randla: in_dim=%d: the input features need at least one channel", in_dim); return SSDR_ERR_UNSUPPORTED; }
     for (int i = 0; i < num_layers; ++i)
         if (d_out[i] != 16 && d_out[i] != 64 && d_out[i] != 128 && d_out[i] != 256 && d_out[i] != 512) { set_error("randla: d_out[%d]=%d is not supported", i, d_out[i]); return SSDR_ERR_UNSUPPORTED; }
     Model* m = new Model();

@@ -53,7 +53,8 @@ class Network:
 
     def set_precision(self, mode):
         """Arithmetic of the matrix products: "f32" (exact, default), "bf16x3" (split bf16, fp32 accumulate; within the
-        1e-3 tolerance of the fp32 path) or "bf16" (BASELINE configuration 3)."""
+        1e-3 tolerance of the fp32 path while the features stay small, as on tiles of a few metres: its error grows with
+        them, ~6e-5 of max |feat32| on 50 m tiles, tests/test_randla_paths.py) or "bf16" (BASELINE configuration 3)."""
         _lib.check(_lib.lib().ssdr_randla_set_precision(self._h, self.PRECISIONS[mode]))
         self.precision = mode
         return self
