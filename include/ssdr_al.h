@@ -236,6 +236,55 @@ void ssdr_randla_destroy(void* handle);
 int  ssdr_randla_infer_dev(void* handle, size_t batch_size, size_t npts, const float* d_features, const float* d_xyz,
                            const int32_t* ratios, int32_t* const* d_neigh_idx, int32_t* const* d_interp_idx,
                            float* d_probs, float* d_feat32, void* stream);
+/* B = 1 with explicit level sizes: level l is the first level_rows[l] rows (level_rows host [num_layers + 1], positive, non-increasing, or
+ * SSDR_ERR_INVALID; more than SSDR_PREDICT_MAX_ROWS level-0 rows: SSDR_ERR_UNSUPPORTED).  neigh_idx[l] [level_rows[l], K] indexes level l,
+ * interp_idx[l] [level_rows[l], 1] level l + 1; rows need not come from one cloud (the packed whole-cloud batch of the prediction pass,
+ * ssdr_predict_*).  ssdr_randla_infer_dev is this call with level_rows[l + 1] = level_rows[l] / ratios[l] and B tiles. */
+int  ssdr_randla_infer_rows_dev(void* handle, const size_t* level_rows, const float* d_features, const float* d_xyz,
+                                int32_t* const* d_neigh_idx, int32_t* const* d_interp_idx, float* d_probs, float* d_feat32, void* stream);
+
+/* ---- whole-cloud prediction pass (TSampler.prediction / compute_features, S3/sampler2.py:580-642, :313-342; csrc/predict.hip) -------
+ * Every cloud goes through the network WHOLE (spatially_regular_gen in mode "sampling", s3dis_dataset.py:129-150): cloud c (n_c points,
+ * rows [cloud_offsets[c], cloud_offsets[c+1]) of the concatenated clouds; cloud_offsets host int64 [num_clouds + 1]) has
+ * T_c = max(n_c, num_points) tile rows; its level l is its first N_c^(l) rows (N^(0) = T_c, N^(l+1) = N^(l) / ratios[l]).
+ * Packed layout: segment s = L .. 0 (deepest first) holds rows [N_c^(s+1), N_c^(s)) of every cloud in turn, so the level-l rows of all
+ * clouds are the first P_l = sum_c N_c^(l) packed rows (the network's prefix levels, ssdr_randla_infer_rows_dev).
+ * Cloud-major layout: cloud c's T_c rows start at row sum_{c' < c} T_c'.  KNN block layout: level l's block starts at row
+ * R_l = sum_{l' < l} P_l', cloud c's N_c^(l) rows follow the clouds before it.
+ * Refused by every entry below: an empty cloud or one too small for the pyramid (SSDR_ERR_INVALID), more than SSDR_PREDICT_MAX_ROWS
+ * level-0 rows or more than 4096 clouds in one call (SSDR_ERR_UNSUPPORTED). */
+#define SSDR_PREDICT_MAX_ROWS (1 << 23)
+/* P_0 .. P_L of a chunk (level_rows host int64 [num_layers + 1], may be NULL: validation only). */
+int ssdr_predict_layout(const int64_t* cloud_offsets, size_t num_clouds, size_t num_points, size_t num_layers, const int32_t* ratios,
+                        int64_t* level_rows);
+/* The whole-cloud tile: tile.hip's rule (ascending float32 squared distance to centers[c], ties by index; row r takes sorted position
+ * d_perm[r] or, for a padded cloud, DP.data_aug's duplicate floor(d_dup_u[r] * n_c) of the shuffled list; coordinates minus the centre)
+ * with num_points = T_c.  d_perm / d_dup_u: [sum T_c], cloud c's T_c draws at its cloud-major offset.  Outputs: cloud-major d_cm_xyz
+ * [sum T_c, 3] and d_cm_idx [sum T_c] (source point inside its cloud = the reference's point_idx); packed d_pk_xyz [P_0, 3], d_pk_feat
+ * [P_0, 6] = [xyz, rgb * color_scale], d_pk_src [P_0] (may be NULL), d_pk_labels [P_0] (may be NULL; needs d_labels [sum n_c]). */
+int ssdr_predict_tile_dev(const float* d_points, const float* d_colors, const int32_t* d_labels, const int64_t* cloud_offsets, size_t num_clouds,
+                          const float* centers, size_t num_points, size_t num_layers, const int32_t* ratios, const int32_t* d_perm, const float* d_dup_u,
+                          float color_scale, float* d_cm_xyz, int32_t* d_cm_idx, float* d_pk_xyz, float* d_pk_feat, int32_t* d_pk_src,
+                          int32_t* d_pk_labels, void* stream);
+/* KNN pyramid of every cloud over its cloud-major rows (ssdr_knn_pyramid_dev per cloud, bit for bit; K = 16 only): d_cm_neigh
+ * [R_L, 16] and d_cm_interp [R_L] in the KNN block layout, values cloud-local rows.  Status through ssdr_knn_status on the stream. */
+int ssdr_knn_pyramid_ragged_dev(const float* d_cm_xyz, const int64_t* cloud_offsets, size_t num_clouds, size_t num_points, size_t num_layers,
+                                const int32_t* ratios, size_t K, int32_t* d_cm_neigh, int32_t* d_cm_interp, void* stream);
+/* Cloud-local KNN tables -> packed: row j of cloud c in level l's block moves to R_l + pos(c, j), every value v to pos(c, v).  Level l of
+ * d_pk_neigh [R_L, 16] / d_pk_interp [R_L] starts at row R_l and is the network's neigh_idx[l] / interp_idx[l]. */
+int ssdr_predict_translate_dev(const int64_t* cloud_offsets, size_t num_clouds, size_t num_points, size_t num_layers, const int32_t* ratios, size_t K,
+                               const int32_t* d_cm_neigh, const int32_t* d_cm_interp, int32_t* d_pk_neigh, int32_t* d_pk_interp, void* stream);
+/* Packed network outputs -> each cloud's own point order: d_probs [sum n_c, num_classes], d_feat32 [sum n_c, 32].
+ * mode SSDR_READBACK_REFERENCE: out[p] = tile_out[argsort(point_idx)[p]] (sampler2.py:599, :327) with a STABLE argsort — on a padded cloud
+ *   point_idx holds duplicates and row p is the p-th smallest key's row, not always point p's (NumPy's default argsort is not stable:
+ *   it may pick another row of the same point, which differs only in rounding);
+ * mode SSDR_READBACK_POINT: point p gets the output of its own first tile row.  Identical for an unpadded cloud.
+ * d_cm_idx is ssdr_predict_tile_dev's: rows [0, n_c) of every cloud hold each of its points once, a padded cloud's duplicates follow. */
+#define SSDR_READBACK_REFERENCE 0
+#define SSDR_READBACK_POINT 1
+int ssdr_predict_readback_dev(const int64_t* cloud_offsets, size_t num_clouds, size_t num_points, size_t num_layers, const int32_t* ratios,
+                              const int32_t* d_cm_idx, const float* d_pk_probs, size_t num_classes, const float* d_pk_feat32, int mode,
+                              float* d_probs, float* d_feat32, void* stream);
 
 /* ---- selection stage (replaces the NumPy / sklearn host code of S3/sampler2.py:12-47,102-115,262-266,313-342,
  *      612-640, S3/fps_gcn_cpu.py:12-178 and S3/kcenterGreedy.py:60-128) ---------------------------------------

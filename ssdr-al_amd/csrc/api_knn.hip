@@ -307,6 +307,50 @@ int ssdr_knn_pyramid_dev(const float* d_xyz, size_t B, size_t npts, size_t num_l
     return leave_ticket(S, s);
 }
 
+// The pyramid of a RAGGED batch (predict.hip's whole clouds): cloud c is T_c = max(n_c, num_points) rows of d_cm_xyz starting at sum_{c' < c} T_c',
+// level l its first N_c^(l) rows.  Sets (l, c) level-major, the K = 16 self-search and its K = 1 up-sampling pairing per cloud exactly as
+// ssdr_knn_pyramid_dev; outputs cloud-major: level l's block starts at row R_l = sum_{l' < l} sum_c N_c^(l'), cloud c's rows follow the clouds
+// before it, values are cloud-local rows.
+int ssdr_knn_pyramid_ragged_dev(const float* d_cm_xyz, const int64_t* cloud_offsets, size_t num_clouds, size_t num_points, size_t num_layers,
+                                const int32_t* ratios, size_t K, int32_t* d_cm_neigh, int32_t* d_cm_interp, void* stream) {
+    if (!d_cm_xyz || !cloud_offsets || !ratios || !d_cm_neigh || !d_cm_interp || num_clouds == 0 || num_points == 0 || num_layers == 0 || num_layers > 16) {
+        set_error("knn_pyramid_ragged: bad arguments"); return SSDR_ERR_INVALID;
+    }
+    if (K != 16) { set_error("knn_pyramid_ragged: K = %zu (the grid search's K = 16 only)", K); return SSDR_ERR_UNSUPPORTED; }
+    if (num_clouds > 4096) { set_error("knn_pyramid_ragged: %zu clouds in one call (at most 4096)", num_clouds); return SSDR_ERR_UNSUPPORTED; }
+    const size_t L = num_layers, nc = num_clouds;
+    std::vector<long> N((L + 1) * nc), row(nc);
+    long rows = 0;
+    for (size_t c = 0; c < nc; ++c) {
+        const long n = (long)(cloud_offsets[c + 1] - cloud_offsets[c]);
+        if (n <= 0) { set_error("knn_pyramid_ragged: cloud %zu is empty", c); return SSDR_ERR_INVALID; }
+        row[c] = rows; N[c] = std::max(n, (long)num_points); rows += N[c];
+        for (size_t l = 0; l < L; ++l) {
+            if (ratios[l] <= 0) { set_error("ratio must be positive"); return SSDR_ERR_INVALID; }
+            N[(l + 1) * nc + c] = N[l * nc + c] / ratios[l];
+        }
+        if (N[L * nc + c] <= 0) { set_error("knn_pyramid_ragged: cloud %zu is too small for the pyramid", c); return SSDR_ERR_INVALID; }
+    }
+    if (rows > SSDR_PREDICT_MAX_ROWS) { set_error("knn_pyramid_ragged: %ld level-0 rows in one call (cap %d)", rows, SSDR_PREDICT_MAX_ROWS); return SSDR_ERR_UNSUPPORTED; }
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream);
+    KnnState& S = st(s);
+    std::vector<GridDesc> sets((L + 1) * nc);
+    for (size_t l = 0; l <= L; ++l)
+        for (size_t c = 0; c < nc; ++c) { GridDesc& d = sets[l * nc + c]; d = GridDesc{}; d.pts = d_cm_xyz + 3 * row[c]; d.n = (int)N[l * nc + c]; }
+    std::vector<GridJob> j16, j1;
+    long r = 0;
+    for (size_t l = 0; l < L; ++l)
+        for (size_t c = 0; c < nc; ++c) {
+            const int n = (int)N[l * nc + c];
+            j16.push_back(GridJob{(int)(l * nc + c), (int)(l * nc + c), n, (int)(L * nc + j1.size()), d_cm_xyz + 3 * row[c], d_cm_neigh + (size_t)r * K,
+                                  (int)N[(l + 1) * nc + c], 0});
+            j1.push_back(GridJob{(int)((l + 1) * nc + c), (int)(l * nc + c), n, -1, d_cm_xyz + 3 * row[c], d_cm_interp + r, 0, 0});
+            r += n;
+        }
+    return grid_knn(S, sets, j16, j1, false, s);
+}
+
 int ssdr_knn_pyramid(const float* xyz, size_t B, size_t npts, size_t num_layers, const int32_t* ratios, size_t K,
                      int32_t* const* neigh_idx, int32_t* const* sub_idx, int32_t* const* interp_idx) {
     if (!xyz || !ratios || !neigh_idx || !interp_idx || num_layers == 0 || num_layers > 16) { set_error("bad pyramid arguments"); return SSDR_ERR_INVALID; }

@@ -263,18 +263,16 @@ void ssdr_randla_destroy(void* handle) {
     delete m;
 }
 
-int ssdr_randla_infer_dev(void* handle, size_t B, size_t n0, const float* d_features, const float* d_xyz,
-                          const int32_t* ratios, int32_t* const* d_neigh_idx, int32_t* const* d_interp_idx,
-                          float* d_probs, float* d_feat32, void* stream) {
-    Model* m = static_cast<Model*>(handle);
-    if (!m || !d_features || !d_xyz || !ratios || !d_neigh_idx || !d_interp_idx || !d_probs || !d_feat32 || B == 0 || n0 == 0) { set_error("randla_infer: bad arguments"); return SSDR_ERR_INVALID; }
-    for (auto& l : m->layers) if (!l.set) { set_error("randla_infer: not every layer has weights"); return SSDR_ERR_INVALID; }
-    SSDR_TRY(ensure_init());
-    hipStream_t s = pick_stream(stream);
+}
+
+namespace ssdr {
+namespace {
+
+// the network over level sizes N[0..L] (B batch elements of n0 level-0 rows each): shared by ssdr_randla_infer_dev (N[l+1] = N[l] / ratio[l])
+// and ssdr_randla_infer_rows_dev (B = 1, packed level sizes)
+int infer_levels(Model* m, size_t B, size_t n0, const std::vector<int>& N, const float* d_features, const float* d_xyz,
+                 int32_t* const* d_neigh_idx, int32_t* const* d_interp_idx, float* d_probs, float* d_feat32, hipStream_t s) {
     const int L = m->L, Bi = (int)B;
-    std::vector<int> N(L + 1); N[0] = (int)n0;
-    for (int i = 0; i < L; ++i) { if (ratios[i] <= 0) { set_error("ratio must be positive"); return SSDR_ERR_INVALID; } N[i + 1] = N[i] / ratios[i]; }
-    if (N[L] <= 0) { set_error("randla_infer: tile too small for the pyramid"); return SSDR_ERR_INVALID; }
 
     // workspaces: per level f_pc, agg(d), agg-mlp, out(2d), sampled(2d); decoder ping-pong; fc1/fc2
     size_t need = 0;
@@ -409,6 +407,45 @@ int ssdr_randla_infer_dev(void* handle, size_t B, size_t n0, const float* d_feat
         SSDR_TRY(launch_head(d_feat32, fc.W.as<float>(), fc.b.as<float>(), Bi * N[0], m->C, d_probs, s));     // fc + softmax
     } else SSDR_TRY(fused);
     return SSDR_OK;
+}
+
+}  // namespace
+}  // namespace ssdr
+
+extern "C" {
+
+int ssdr_randla_infer_dev(void* handle, size_t B, size_t n0, const float* d_features, const float* d_xyz,
+                          const int32_t* ratios, int32_t* const* d_neigh_idx, int32_t* const* d_interp_idx,
+                          float* d_probs, float* d_feat32, void* stream) {
+    Model* m = static_cast<Model*>(handle);
+    if (!m || !d_features || !d_xyz || !ratios || !d_neigh_idx || !d_interp_idx || !d_probs || !d_feat32 || B == 0 || n0 == 0) { set_error("randla_infer: bad arguments"); return SSDR_ERR_INVALID; }
+    for (auto& l : m->layers) if (!l.set) { set_error("randla_infer: not every layer has weights"); return SSDR_ERR_INVALID; }
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream);
+    const int L = m->L;
+    std::vector<int> N(L + 1); N[0] = (int)n0;
+    for (int i = 0; i < L; ++i) { if (ratios[i] <= 0) { set_error("ratio must be positive"); return SSDR_ERR_INVALID; } N[i + 1] = N[i] / ratios[i]; }
+    if (N[L] <= 0) { set_error("randla_infer: tile too small for the pyramid"); return SSDR_ERR_INVALID; }
+    return infer_levels(m, B, n0, N, d_features, d_xyz, d_neigh_idx, d_interp_idx, d_probs, d_feat32, s);
+}
+
+int ssdr_randla_infer_rows_dev(void* handle, const size_t* level_rows, const float* d_features, const float* d_xyz,
+                               int32_t* const* d_neigh_idx, int32_t* const* d_interp_idx, float* d_probs, float* d_feat32, void* stream) {
+    Model* m = static_cast<Model*>(handle);
+    if (!m || !level_rows || !d_features || !d_xyz || !d_neigh_idx || !d_interp_idx || !d_probs || !d_feat32) { set_error("randla_infer_rows: bad arguments"); return SSDR_ERR_INVALID; }
+    for (auto& l : m->layers) if (!l.set) { set_error("randla_infer_rows: not every layer has weights"); return SSDR_ERR_INVALID; }
+    const int L = m->L;
+    if (level_rows[0] > SSDR_PREDICT_MAX_ROWS) { set_error("randla_infer_rows: %zu level-0 rows (cap %d = 2^23: int32 element offsets)", level_rows[0], SSDR_PREDICT_MAX_ROWS); return SSDR_ERR_UNSUPPORTED; }
+    std::vector<int> N(L + 1);
+    for (int i = 0; i <= L; ++i) {
+        if (level_rows[i] == 0 || (i > 0 && level_rows[i] > level_rows[i - 1])) {
+            set_error("randla_infer_rows: level table must be positive and non-increasing (level %d: %zu rows, level above: %zu)", i, level_rows[i], i > 0 ? level_rows[i - 1] : 0);
+            return SSDR_ERR_INVALID;
+        }
+        N[i] = (int)level_rows[i];
+    }
+    SSDR_TRY(ensure_init());
+    return infer_levels(m, 1, level_rows[0], N, d_features, d_xyz, d_neigh_idx, d_interp_idx, d_probs, d_feat32, pick_stream(stream));
 }
 
 }

@@ -133,6 +133,12 @@ def lib():
         L.ssdr_knn_status_poll.argtypes = [vp, vp]
         L.ssdr_grid_subsample_status.argtypes = [vp, vp]
         L.ssdr_grid_subsample_set_method.argtypes = [i32]
+        L.ssdr_randla_infer_rows_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.ssdr_predict_layout.argtypes = [vp, sz, sz, sz, vp, vp]
+        L.ssdr_predict_tile_dev.argtypes = [vp, vp, vp, vp, sz, vp, sz, sz, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp]
+        L.ssdr_knn_pyramid_ragged_dev.argtypes = [vp, vp, sz, sz, sz, vp, sz, vp, vp, vp]
+        L.ssdr_predict_translate_dev.argtypes = [vp, sz, sz, sz, vp, sz, vp, vp, vp, vp, vp]
+        L.ssdr_predict_readback_dev.argtypes = [vp, sz, sz, sz, vp, vp, vp, sz, vp, i32, vp, vp, vp]
         _lib = _libs[path] = L
     return _lib
 
