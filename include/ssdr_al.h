@@ -417,6 +417,34 @@ int ssdr_fps_dev(const double* d_feat, size_t n, int feat_dim, int start, size_t
 /* farthest_superpoint_sample (sampler2.py:49-80, "edcd" branch) over one cloud's superpoints, from the centres and
  * directed chamfer means ssdr_cloud_graph_dev produced: distance = |centre_i - centre_c|^2 + CD(i,c); n <= 8192 */
 int ssdr_fps_superpoint_dev(const double* d_centres, const double* d_cd_dir, size_t n, int start, size_t count, int32_t* d_out, void* stream);
+/* farthest_superpoint_sample of MANY clouds in one launch (one workgroup per cloud; the "edcd" branch, sampler2.py:49-80, :670-685): cloud b's rows are
+ * d_coff[b] .. d_coff[b+1]-1 of d_centres [rows, 3] (ssdr_cloud_graph_batch_dev), its directed chamfer means the n_b x n_b block at d_boff[b] of d_cd_dir,
+ * which the call OVERWRITES with dir + dir^T (diagonal 0).  Cloud b picks d_ntop[b] <= n_b rows from its first one, with ssdr_fps_superpoint_dev's arithmetic;
+ * the picks (row indices) are written cloud by cloud at the exclusive prefix of d_ntop, FPS order inside a cloud, max_select >= their sum.  n_max >= every
+ * n_b with picks, n_max <= 8192.  d_status (optional, device int32): set to 0 or to what the device found (4: a cloud above n_max rows, 8: more picks than
+ * rows, 16: more than max_select picks in all); nothing is picked then. */
+int ssdr_edcd_fps_batch_dev(const double* d_centres, double* d_cd_dir, const int32_t* d_coff, const int64_t* d_boff, const int32_t* d_ntop, size_t num_clouds,
+                            size_t n_max, size_t max_select, int32_t* d_out, int32_t* d_status, void* stream);
+/* sampling()'s "edcd" branch behind the candidate rule, ONE enqueue-only call: the arguments and the candidate rule of ssdr_gcn_fps_sampling_dev without
+ * features, labelled rows or GCN (the branch draws no labelled rows), the candidates' bbox centres and directed chamfer means — float64 whatever
+ * ssdr_select_set_chamfer_mode says (the Semantic3D edcd branch uses gcn.chamfer_distance, a float64 KDTree) — and ssdr_edcd_fps_batch_dev over every
+ * cloud.  cap_rows >= the candidates, cap_nmax >= the largest cloud's, cap_sq >= the sum of their squares, max_select = min(batch_size, unlabelled regions).
+ * d_result [8 + max_select + cap_rows] as ssdr_gcn_fps_sampling_dev's: [0..7] counts (n_unl, 0, rows, largest block, picks, status, block elements),
+ * the picks (indices into the candidate list, cloud ascending, FPS order inside a cloud), the candidate list.  Status bits 0-1 as there; 4: a cloud has
+ * more than 8192 candidates (or more than cap_nmax); 8, 16 as above: nothing was selected. */
+int ssdr_edcd_sampling_dev(const float* d_xyz, const int32_t* d_sp_off, const int32_t* d_sp_pts, const int32_t* d_order, size_t S, const uint8_t* d_labelled,
+                           const int32_t* d_sp_base, size_t num_clouds, size_t batch_size, size_t cap_rows, size_t cap_nmax, size_t cap_sq, size_t max_select,
+                           int32_t* d_result, void* stream);
+/* The same for the sharded run: the candidate rule over the GLOBAL ranking as ssdr_gcn_fps_sharded_local_dev takes it (d_gorder [Sg = world * Smax],
+ * d_glabelled, d_gbase [world * Bmax + 1]), then this rank's clouds' graphs and picks.  edcd is per cloud: no exchange follows.  d_result as above for
+ * this rank alone: its candidates (local region ids), its picks (indices into them; counts[4] = its share of sampling_batch). */
+int ssdr_edcd_sampling_sharded_dev(const float* d_xyz, const int32_t* d_sp_off, const int32_t* d_sp_pts, size_t num_clouds, const int32_t* d_gorder, size_t Sg,
+                                   const uint8_t* d_glabelled, const int32_t* d_gbase, int rank, int world, size_t Smax, size_t Bmax, size_t batch_size,
+                                   size_t cap_rows, size_t cap_nmax, size_t cap_sq, size_t max_select, int32_t* d_result, void* stream);
+/* sampling()'s last branch, uncertainty alone (sampler2.py:783-806): the first min(batch_size, population) entries of the ranking d_order [n] whose
+ * d_skip[id] == 0, in rank order; of them, the ids in [lo, hi) are written to d_out as id - lo (a sharded rank keeps its own: lo = rank * Smax).
+ * d_res[0] = entries written, d_res[1] = the size of the whole top.  d_out holds min(batch_size, hi - lo). */
+int ssdr_topk_regions_dev(const int32_t* d_order, size_t n, const uint8_t* d_skip, size_t batch_size, size_t lo, size_t hi, int32_t* d_res, int32_t* d_out, void* stream);
 /* kCenterGreedy.select_batch_ (kcenterGreedy.py:84-128) with direct float64 Euclidean distances */
 int ssdr_kcenter_dev(const double* d_feat, size_t n, int feat_dim, const int32_t* d_already_selected, size_t n_already, size_t count,
                      int32_t* d_out, void* stream);

@@ -14,6 +14,7 @@
 #include <map>
 #include "block_prims.hpp"
 #include "select_chamfer.hpp"
+#include "select_region.hpp"
 
 namespace ssdr {
 namespace {
@@ -2652,6 +2653,87 @@ int ssdr_fps_gathered_dev(const double* d_gathered, const int32_t* d_plan, int w
                        d_plan + 8, repeat, nrep);
     SSDR_HIP(hipGetLastError());
     return fps_like(d_glob, cap_rows, 32, nullptr, 0, start, max_select, 0, d_out, s, nrep);
+}
+
+/* sampling()'s "edcd" branch (sampler2.py:670-685) behind the candidate rule, as one enqueue-only chain: the same candidate rule as the gcn_fps chain with no
+ * labelled rows (the branch draws none), the candidates' bbox centres and directed chamfer means, always in float64 (the Semantic3D code's edcd branch
+ * uses gcn.chamfer_distance, a float64 KDTree, SSRD_AL_semantic3d/sampler2.py:51-80, whatever its GCN_FPS_sampling uses), then every cloud's
+ * farthest_superpoint_sample in one launch (select_region.hip).  The two entry points below differ in their candidate rule only. */
+static int edcd_graph_fps(SelState& Q, const float* d_xyz, const int32_t* d_sp_off, const int32_t* d_sp_pts, const int* gsel, const int* coff, const long long* boff,
+                          const int* ntop, int B, size_t cap_rows, size_t cap_nmax, size_t max_select, int* ooff, double* cen, double* dir, int32_t* d_result, hipStream_t s) {
+    const int nm = (int)cap_nmax; const unsigned nc = (unsigned)B;
+    std::optional<ProfScope> prof; prof.emplace("sel_features_pack", s, 0.0);
+    ChamferPack P; SSDR_TRY(chamfer_pack_buffers(Q, cap_rows, (size_t)B, P));
+    SSDR_TRY(chamfer_pack_launch(P, d_xyz, d_sp_off, d_sp_pts, gsel, coff, 0, cap_rows, nm, nc, cen, s));
+    prof.emplace("sel_chamfer", s, 0.0);
+    SSDR_TRY(chamfer_dir_batch_launch(d_xyz, d_sp_off, d_sp_pts, gsel, coff, boff, nm, nc, cen, dir, P, s, 0));
+    prof.reset();
+    SSDR_HIP(hipGetLastError());
+    return edcd_fps_launch(cen, dir, coff, boff, ntop, B, nm, (long long)max_select, ooff, d_result + 5, d_result + 8, s);
+}
+
+int ssdr_edcd_sampling_dev(const float* d_xyz, const int32_t* d_sp_off, const int32_t* d_sp_pts, const int32_t* d_order, size_t S, const uint8_t* d_labelled,
+                           const int32_t* d_sp_base, size_t num_clouds, size_t batch_size, size_t cap_rows, size_t cap_nmax, size_t cap_sq, size_t max_select,
+                           int32_t* d_result, void* stream) {
+    if (!d_xyz || !d_sp_off || !d_sp_pts || !d_order || !d_labelled || !d_sp_base || !d_result || num_clouds == 0 || num_clouds > 65535 || S == 0 || S > 0x7ffffff0 ||
+        cap_rows == 0 || cap_nmax == 0 || cap_sq == 0 || cap_rows > (1u << 22) || max_select > 0x7fffffff) {
+        set_error("edcd_sampling: bad arguments (at most 2^22 candidates, at most 65535 clouds)"); return SSDR_ERR_INVALID;
+    }
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream); SelState& Q = sst(s);
+    const int B = (int)num_clouds, nchunks = (int)((S + CR_NT - 1) / CR_NT);
+    // ints: rankpos S, cploc S, stage S, chunk nchunks, ncand B, ntop B, uoff / coff / lab_off / ooff B+1 each, gsel cap, rows cap | int64: boff B+1
+    const size_t ni = 3 * S + (size_t)nchunks + 6 * (size_t)B + 4 + 2 * cap_rows + 16;
+    SSDR_TRY(Q.cand_i.reserve(4 * ni + 8 * ((size_t)B + 2)));
+    int* rankpos = Q.cand_i.as<int>(); int* cploc = rankpos + S; int* stage = cploc + S; int* chunk = stage + S; int* ncand = chunk + nchunks; int* ntop = ncand + B;
+    int* uoff = ntop + B; int* coff = uoff + B + 1; int* lab_off = coff + B + 1; int* ooff = lab_off + B + 1; int* gsel = ooff + B + 1; int* rows = gsel + cap_rows;
+    long long* boff = reinterpret_cast<long long*>(Q.cand_i.as<char>() + ((4 * ni + 7) & ~(size_t)7));
+    SSDR_TRY(Q.cand_f.reserve(8 * (3 * cap_rows + cap_sq)));
+    double* cen = Q.cand_f.as<double>(); double* dir = cen + 3 * cap_rows;
+    int* counts = d_result; int* sel = d_result + 8 + max_select;
+    SSDR_HIP(hipMemsetAsync(lab_off, 0, 4 * ((size_t)B + 1), s));
+    std::optional<ProfScope> prof; prof.emplace("sel_candidate_rule", s, 0.0);
+    hipLaunchKernelGGL(cand_rank, dim3(nchunks), dim3(CR_NT), 0, s, d_order, (int)S, d_labelled, rankpos, cploc, chunk);
+    hipLaunchKernelGGL(cand_chunkscan, dim3(1), dim3(256), 0, s, chunk, nchunks);
+    hipLaunchKernelGGL(cand_cloud, dim3(B, cand_slices(S, (size_t)B)), dim3(256), 0, s, rankpos, cploc, chunk, d_labelled, d_sp_base, (int)S, (int)std::min<size_t>(batch_size, 0x7fffffff), stage, ncand, ntop);
+    hipLaunchKernelGGL(cand_layout, dim3(1), dim3(256), 0, s, ncand, ntop, lab_off, B, (long long)cap_rows, (long long)cap_sq, uoff, coff, boff, counts);
+    hipLaunchKernelGGL(cand_fill, dim3(B), dim3(256), 0, s, stage, d_sp_base, ncand, uoff, coff, lab_off, (const int*)nullptr, counts, sel, gsel, rows, (int*)nullptr);
+    SSDR_HIP(hipGetLastError());
+    prof.reset();
+    return edcd_graph_fps(Q, d_xyz, d_sp_off, d_sp_pts, gsel, coff, boff, ntop, B, cap_rows, cap_nmax, max_select, ooff, cen, dir, d_result, s);
+}
+
+int ssdr_edcd_sampling_sharded_dev(const float* d_xyz, const int32_t* d_sp_off, const int32_t* d_sp_pts, size_t num_clouds, const int32_t* d_gorder, size_t Sg,
+                                   const uint8_t* d_glabelled, const int32_t* d_gbase, int rank, int world, size_t Smax, size_t Bmax, size_t batch_size,
+                                   size_t cap_rows, size_t cap_nmax, size_t cap_sq, size_t max_select, int32_t* d_result, void* stream) {
+    if (!d_xyz || !d_sp_off || !d_sp_pts || !d_gorder || !d_glabelled || !d_gbase || !d_result || world < 1 || world > 64 || rank < 0 || rank >= world || num_clouds == 0 ||
+        num_clouds > Bmax || Bmax * (size_t)world > 65535 || Sg != Smax * (size_t)world || Sg > 0x7ffffff0 || cap_rows == 0 || cap_nmax == 0 || cap_sq == 0 ||
+        cap_rows > (1u << 22) || max_select > 0x7fffffff) {
+        set_error("edcd_sampling_sharded: bad arguments (world <= 64, Sg == world * Smax, at most 2^22 candidates)"); return SSDR_ERR_INVALID;
+    }
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream); SelState& Q = sst(s);
+    const int Bg = (int)(Bmax * (size_t)world), B = (int)num_clouds, nchunks = (int)((Sg + CR_NT - 1) / CR_NT);
+    const size_t ni = 3 * Sg + (size_t)nchunks + 2 * (size_t)Bg + 4 * (size_t)B + 4 + 2 * cap_rows + 16;
+    SSDR_TRY(Q.cand_i.reserve(4 * ni + 8 * ((size_t)B + 2)));
+    int* rankpos = Q.cand_i.as<int>(); int* cploc = rankpos + Sg; int* stage = cploc + Sg; int* chunk = stage + Sg; int* ncand = chunk + nchunks; int* ntop = ncand + Bg;
+    int* uoff = ntop + Bg; int* coff = uoff + B + 1; int* lab_off = coff + B + 1; int* ooff = lab_off + B + 1; int* gsel = ooff + B + 1; int* rows = gsel + cap_rows;
+    long long* boff = reinterpret_cast<long long*>(Q.cand_i.as<char>() + ((4 * ni + 7) & ~(size_t)7));
+    SSDR_TRY(Q.cand_f.reserve(8 * (3 * cap_rows + cap_sq)));
+    double* cen = Q.cand_f.as<double>(); double* dir = cen + 3 * cap_rows;
+    int* counts = d_result; int* sel = d_result + 8 + max_select;
+    const size_t rb = (size_t)rank * Bmax;
+    SSDR_HIP(hipMemsetAsync(lab_off, 0, 4 * ((size_t)B + 1), s));
+    std::optional<ProfScope> prof; prof.emplace("sel_candidate_rule", s, 0.0);
+    hipLaunchKernelGGL(cand_rank, dim3(nchunks), dim3(CR_NT), 0, s, d_gorder, (int)Sg, d_glabelled, rankpos, cploc, chunk);
+    hipLaunchKernelGGL(cand_chunkscan, dim3(1), dim3(256), 0, s, chunk, nchunks);
+    hipLaunchKernelGGL(cand_cloud, dim3(Bg, cand_slices(Sg, (size_t)Bg)), dim3(256), 0, s, rankpos, cploc, chunk, d_glabelled, d_gbase, (int)Sg, (int)std::min<size_t>(batch_size, 0x7fffffff), stage, ncand, ntop);
+    // this rank's clouds: counts[4] = its picks; edcd is per cloud, so nothing of the other ranks is needed
+    hipLaunchKernelGGL(cand_layout, dim3(1), dim3(256), 0, s, ncand + rb, ntop + rb, lab_off, B, (long long)cap_rows, (long long)cap_sq, uoff, coff, boff, counts);
+    hipLaunchKernelGGL(cand_fill_local, dim3(B), dim3(256), 0, s, stage, d_gbase + rb, ncand + rb, uoff, coff, lab_off, (const int*)nullptr, counts, (int)((size_t)rank * Smax), sel, gsel, rows);
+    SSDR_HIP(hipGetLastError());
+    prof.reset();
+    return edcd_graph_fps(Q, d_xyz, d_sp_off, d_sp_pts, gsel, coff, boff, ntop + rb, B, cap_rows, cap_nmax, max_select, ooff, cen, dir, d_result, s);
 }
 
 int ssdr_fps_superpoint_dev(const double* d_centres, const double* d_cd_dir, size_t n, int start, size_t count, int32_t* d_out, void* stream) {

@@ -665,8 +665,8 @@ int chamfer_dir_launch(const float* d_xyz, const int* d_sp_off, const int* d_sp_
 }
 
 int chamfer_dir_batch_launch(const float* d_xyz, const int* d_sp_off, const int* d_sp_pts, const int* d_sel, const int* d_coff, const long long* d_boff,
-                             int n_max, unsigned nclouds, const double* d_centres, double* d_dir, const ChamferPack& P, hipStream_t s) {
-    if (g_chamfer_mode.load() == 1) {
+                             int n_max, unsigned nclouds, const double* d_centres, double* d_dir, const ChamferPack& P, hipStream_t s, int mode) {
+    if ((mode < 0 ? g_chamfer_mode.load() : mode) == 1) {
         hipLaunchKernelGGL(sel_chamfer_dir_f32_batch, dim3((unsigned)std::min<long>(((long)n_max * n_max + 3) / 4, 16384), 1, nclouds), dim3(256), 0, s, d_xyz, d_sp_off, d_sp_pts, d_sel,
                            d_coff, d_boff, d_centres, d_dir);
         SSDR_HIP(hipGetLastError());

@@ -61,7 +61,8 @@ __device__ __forceinline__ uint4 source_operand(double u, double v, int h) {
 // its n_c x n_c block in dir).  n_max = the largest cloud's superpoints.
 int chamfer_dir_launch(const float* d_xyz, const int* d_sp_off, const int* d_sp_pts, const int* d_sel, int n, const double* d_centres, double* d_dir,
                        const ChamferPack& P, hipStream_t s);
+// mode: 0 float64, 1 float32 (ssdr_select_set_chamfer_mode), -1 the process-wide setting
 int chamfer_dir_batch_launch(const float* d_xyz, const int* d_sp_off, const int* d_sp_pts, const int* d_sel, const int* d_coff, const long long* d_boff,
-                             int n_max, unsigned nclouds, const double* d_centres, double* d_dir, const ChamferPack& P, hipStream_t s);
+                             int n_max, unsigned nclouds, const double* d_centres, double* d_dir, const ChamferPack& P, hipStream_t s, int mode = -1);
 
 }  // namespace ssdr

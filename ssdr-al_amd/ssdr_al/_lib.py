@@ -102,6 +102,10 @@ def lib():
         L.ssdr_create_adj_dev.argtypes = [vp, sz, i32, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp]
         L.ssdr_gcn_fps_sampling_dev.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, sz, i32, i32, i32, i32, sz, sz, sz, sz, sz, vp, vp]
         L.ssdr_fps_superpoint_dev.argtypes = [vp, vp, sz, i32, sz, vp, vp]
+        L.ssdr_edcd_fps_batch_dev.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp]
+        L.ssdr_edcd_sampling_dev.argtypes = [vp, vp, vp, vp, sz, vp, vp, sz, sz, sz, sz, sz, sz, vp, vp]
+        L.ssdr_edcd_sampling_sharded_dev.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, i32, i32, sz, sz, sz, sz, sz, sz, sz, vp, vp]
+        L.ssdr_topk_regions_dev.argtypes = [vp, sz, vp, sz, sz, sz, vp, vp, vp]
         L.ssdr_gcn_fps_sharded_local_dev.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, i32, i32, sz, sz, sz, i32, i32, sz, sz, sz, sz, sz, vp, vp, vp]
         L.ssdr_event_create.argtypes = [C.POINTER(vp)]; L.ssdr_event_record.argtypes = [vp, vp]; L.ssdr_stream_wait_event.argtypes = [vp, vp]; L.ssdr_event_destroy.argtypes = [vp]
         L.ssdr_select_set_chamfer_mode.argtypes = [i32]

@@ -47,6 +47,23 @@ class _Pairs:
         return repr(self.tolist())
 
 
+SELECTORS = ("fps", "kcenter", "edcd", "topk")
+
+
+def selector_for(sampler_args):
+    """The selector that runs the branch of TSampler.sampling() a reference `sampler_args` names, tested in the reference's elif order
+    (sampler2.py:670, :687, :736, :783): "edcd", "gcn" (not offered), "gcn_fps", else uncertainty alone."""
+    args = list(sampler_args)
+    if "edcd" in args:
+        return "edcd"
+    if "gcn" in args:
+        raise ValueError('sampler_args names the "gcn" branch (a GCN trained during selection, sampler2.py:687-734), which is out of scope here; '
+                         'selector="kcenter" runs its last step (kCenterGreedy over candidates + labelled regions)')
+    if "gcn_fps" in args:
+        return "fps"
+    return "topk"
+
+
 class HotPath:
     def __init__(self, weights, config=ConfigS3DIS, sampler_args=("sb", "WetSU", "clsbal", "gcn_fps"), gcn_number=1, gcn_top=0,
                  select_per_tile=37, labeled_per_tile=15, seed=0, precision="f32", selector="fps", tiles32=True, min_size=1, round_num=5,
@@ -69,8 +86,10 @@ class HotPath:
         self.label_seed = int(seed if label_seed is None else label_seed)
         # "fps": farthest_features_sample over the candidates' propagated features (the gcn_fps branch, sampler2.py:736-781);
         # "kcenter": kCenterGreedy.select_batch_ over candidates + labelled regions with the labelled ones as already selected
-        # (the step the reference's gcn branch ends with, gcn.py:247, kcenterGreedy.py:60-128; BASELINE configuration 4's global k-center)
-        assert selector in ("fps", "kcenter")
+        # (the step the reference's gcn branch ends with, gcn.py:247, kcenterGreedy.py:60-128; BASELINE configuration 4's global k-center);
+        # "edcd": every cloud's farthest_superpoint_sample over its candidates (sampler2.py:670-685, :49-80), always with the float64 chamfer;
+        # "topk": the first batch_size regions of the ranking (sampler2.py:783-806).  selector_for() maps a reference sampler_args to one of them
+        assert selector in SELECTORS, "selector must be one of %s" % (SELECTORS,)
         self.selector = selector
         self.fps_start = 0          # np.random.randint(0, n) in the reference (fps_gcn_cpu.py:133); fixed here
         self.stream = None          # stream of the pyramid .. scoring stages (None = the library's main stream)
@@ -271,7 +290,16 @@ class HotPath:
         for i in np.argsort(-(share + nlab), kind="stable"):
             a = int(min(share[i], left)); left -= a
             sq += (a + int(nlab[i])) ** 2
-        self._sel_static = dict(
+        region = {}
+        if self.selector == "edcd":      # the edcd round's rows are the candidates alone (the branch draws no labelled rows)
+            left, sq_e = cap_unl, 0
+            for i in np.argsort(-share, kind="stable"):
+                a = int(min(share[i], left)); left -= a
+                sq_e += a * a
+            region = dict(e_cap_nmax=max(int(share.max()) if B else 1, 1), e_cap_sq=max(int(sq_e), 1))
+        elif self.selector == "topk":
+            region = dict(d_topk=DevArray((8 + max(min(batch, S), 1),), np.int32))
+        self._sel_static = dict(region,
             lab_cloud=np.repeat(np.arange(B, dtype=np.int64), nlab), lab_sp_h=lab_sp[:-1].astype(np.int64),
             d_lab=DevArray.from_host(self.skip_mask.astype(np.uint8)), d_base=DevArray.from_host(base.astype(np.int32)),
             d_lab_off=DevArray.from_host(lab_off), d_lab_sp=DevArray.from_host(lab_sp), n_lab=int(nlab.sum()), batch=batch, picks=picks, cap_unl=max(cap_unl, 1),
@@ -373,6 +401,18 @@ class HotPath:
                    d_send=DevArray((per, 32), np.float64), d_gath=DevArray((W, per, 32), np.float64), d_glob=DevArray((cap_fps + n_lab_all + 1, 32), np.float64),
                    d_nlab_off=DevArray.from_host(np.concatenate([[0], np.cumsum(nlab)]).astype(np.int32)), d_already=DevArray((max(n_lab_all, 1),), np.int32),
                    d_plan=DevArray((16 + W + 2 * W * nu_dev,), np.int32), d_out=DevArray((max(rep * picks, 1),), np.int32))
+        if self.selector == "edcd":      # this rank's share of the edcd round: its own candidates and picks, no labelled rows
+            own = int(min(batch, nvalid_c.sum()))
+            cap_e = int(min(2 * own, nvalid_c.sum()))
+            share_e = np.minimum(2 * own, nvalid_c)
+            left, sq_e = cap_e, 0
+            for i in np.argsort(-share_e, kind="stable"):
+                a = int(min(share_e[i], left)); left -= a
+                sq_e += a * a
+            dev.update(e_picks=own, e_cap_rows=max(cap_e, 1), e_cap_nmax=max(int(share_e.max()) if self.B else 1, 1), e_cap_sq=max(int(sq_e), 1),
+                       e_result=DevArray((8 + own + max(cap_e, 1),), np.int32))
+        elif self.selector == "topk":
+            dev.update(t_result=DevArray((8 + max(min(batch, self.S), 1),), np.int32))
         self._dist = dict(dev=dev, comm=comm, Smax=Smax, Bmax=Bmax, valid=lab == 0, gcloud=gcloud, room=room, spin=spin, batch=batch,
                           S_total=int(S_all[:, 0].sum()), n_pop=int(nvalid_all.sum()), nu_max=int(min(2 * batch, Smax)),
                           nlab=nlab,
@@ -419,7 +459,7 @@ class HotPath:
         """kept for callers of the two-step form: the exchanges are enqueued by _score_async and nothing waits on the host any more"""
         return
 
-    def _candidates(self, order, valid, cloud, batch_size):
+    def _candidates(self, order, valid, cloud, batch_size, with_top=False):
         """create_file_top_and_all + the candidate rule of sampling() (sampler2.py:533-552, :745-753) on index lists: `order` ranks
         the regions by descending uncertainty, valid[i] = region i may compete (not labelled), cloud[i] = its cloud.  Returns the
         candidates (cloud ascending, descending uncertainty inside a cloud) and their clouds, and the number to select.
@@ -437,6 +477,8 @@ class HotPath:
         first = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64) if nc else np.zeros(0, np.int64)
         pos = np.arange(len(cand)) - first[c]
         take = pos < 2 * ntop[c]                              # candidates = first 2 x selected_num of the cloud (:748)
+        if with_top:                                          # (the edcd round also needs selected_num per cloud)
+            return cand[take], c[take], int(ntop.sum()), ntop
         return cand[take], c[take], int(ntop.sum())
 
     def _select(self, comm=None):
@@ -445,6 +487,8 @@ class HotPath:
 
     def _select_issue(self, comm=None):
         """everything of the selection up to the enqueued FPS chain (the host decisions and uploads happen here)"""
+        if self.selector in ("edcd", "topk"):
+            return self._select_issue_region(comm)
         L = _lib.lib()
         st = self.sel_stream          # None: the library stream; a stream of its own lets the selections of consecutive batches overlap
         _lib.check(L.ssdr_select_set_chamfer_mode(self.chamfer_mode))
@@ -585,6 +629,83 @@ class HotPath:
         self._keep = keep
         self._pending = (d_out, unl)
 
+    def _select_issue_region(self, comm=None):
+        """_select_issue of the "edcd" and "topk" selectors.  Device rule (default): one enqueue-only call over the ranking, single-process or sharded,
+        nothing read back here.  SSDR_SELECT_HOST_RULE: the candidate rule / the top on the host, then (edcd) the batched graph and the batched FPS.
+        (sel, unl) keep their contract: edcd's unl = the candidate list (cloud ascending, descending uncertainty inside a cloud) and sel indexes it;
+        topk's unl = the top regions in rank order and sel = arange.  A sharded rank returns its own clouds' share."""
+        L = _lib.lib()
+        st = self.sel_stream
+        T = self._sel_static
+        edcd = self.selector == "edcd"
+        D = self.global_order
+        if not os.environ.get("SSDR_SELECT_HOST_RULE"):
+            if D is None and edcd:
+                _lib.check(L.ssdr_edcd_sampling_dev(self.xyz.ptr, self.sp_off.ptr, self.sp_pts.ptr, self.sorted_inds.ptr, self.S, T["d_lab"].ptr, T["d_base"].ptr, self.B,
+                                                    T["batch"], T["cap_unl"], T["e_cap_nmax"], T["e_cap_sq"], T["picks"], T["d_result"].ptr, st))
+                self._pending = ("device", (T["d_result"], T["picks"]))
+            elif D is None:
+                _lib.check(L.ssdr_topk_regions_dev(self.sorted_inds.ptr, self.S, T["d_lab"].ptr, T["batch"], 0, self.S, T["d_topk"].ptr, T["d_topk"].ptr + 32, st))
+                self._pending = ("topk", T["d_topk"])
+            else:
+                V = D["dev"]; lo = comm.rank * D["Smax"]
+                if edcd:
+                    _lib.check(L.ssdr_edcd_sampling_sharded_dev(self.xyz.ptr, self.sp_off.ptr, self.sp_pts.ptr, self.B, D["d_ord"].ptr, comm.world * D["Smax"], V["d_glab"].ptr,
+                                                                V["d_gbase"].ptr, comm.rank, comm.world, D["Smax"], D["Bmax"], D["batch"], V["e_cap_rows"], V["e_cap_nmax"],
+                                                                V["e_cap_sq"], V["e_picks"], V["e_result"].ptr, st))
+                    self._pending = ("device", (V["e_result"], V["e_picks"]))
+                else:
+                    _lib.check(L.ssdr_topk_regions_dev(D["d_ord"].ptr, comm.world * D["Smax"], V["d_glab"].ptr, D["batch"], lo, lo + self.S, V["t_result"].ptr,
+                                                       V["t_result"].ptr + 32, st))
+                    self._pending = ("topk", V["t_result"])
+            self.rule_path = "device" if D is None else "sharded-device"
+            return
+        self.rule_path = "host"
+        if D is None:
+            order, valid, cloud, batch, sub_c, sub_s = self.sorted_inds.to_host(st), ~self.skip_mask, self.sp_cloud_h, T["batch"], 0, 0
+            room = np.asarray(self.room_ids, np.int64)[self.sp_cloud_h]
+            spin = np.arange(self.S) - np.asarray(self.sp_base, np.int64)[self.sp_cloud_h]
+        else:
+            order, valid, cloud, batch, sub_c, sub_s = D["d_ord"].to_host(st), D["valid"], D["gcloud"], D["batch"], comm.rank * D["Bmax"], comm.rank * D["Smax"]
+            room, spin = D["room"], D["spin"]
+        order = np.asarray(order, np.int64)
+        if not edcd:                          # the top: the first batch_size regions of the population in rank order, this rank's own kept
+            top = order[valid[order]][: batch]
+            top = top[(top >= sub_s) & (top < sub_s + self.S)]
+            loc = top - sub_s
+            self.unl_cloud_ids, self.unl_sp = room[top], spin[top]
+            self._pending = (np.arange(len(loc), dtype=np.int32), _Pairs(self.sp_cloud_h[loc], loc))
+            return
+        cand, ccloud, _, ntop = self._candidates(order, valid, cloud, batch, with_top=True)
+        mine = (cand >= sub_s) & (cand < sub_s + self.S)
+        gcand = cand[mine]
+        cand, ccloud = gcand - sub_s, ccloud[mine] - sub_c
+        ntop = np.concatenate([ntop, np.zeros(max(sub_c + self.B - len(ntop), 0), np.int64)])[sub_c: sub_c + self.B]
+        unl = _Pairs(ccloud, cand)
+        self.unl_cloud_ids, self.unl_sp = room[gcand], spin[gcand]
+        live = np.flatnonzero(ntop > 0)       # the clouds with picks are the clouds with candidates (a cloud offers min(2 x its picks, its regions))
+        picks = int(ntop.sum())
+        if picks == 0:
+            self._pending = (np.zeros(0, np.int32), unl)
+            return
+        n_c = np.bincount(ccloud, minlength=self.B)[live].astype(np.int64)
+        if int(n_c.max()) > 8192:
+            raise RuntimeError("edcd: a cloud has %d candidates; the batched farthest_superpoint_sample takes at most 8192" % int(n_c.max()))
+        coff = np.concatenate([[0], np.cumsum(n_c)]).astype(np.int32)
+        boff = np.concatenate([[0], np.cumsum(n_c * n_c)]).astype(np.int64)
+        d_sel = DevArray.from_host(cand.astype(np.int32), st); d_coff = DevArray.from_host(coff, st); d_boff = DevArray.from_host(boff, st)
+        d_ntop = DevArray.from_host(ntop[live].astype(np.int32), st)
+        ntot, nmax, nsq = int(coff[-1]), int(n_c.max()), int(boff[-1])
+        d_cen = DevArray((ntot, 3), np.float64); d_dir = DevArray((nsq,), np.float64); d_adj = DevArray((nsq,), np.float64)
+        _lib.check(L.ssdr_select_set_chamfer_mode(0))        # the float64 chamfer, whatever chamfer_mode says (the device chain passes it itself)
+        _lib.check(L.ssdr_cloud_graph_batch_dev(self.xyz.ptr, self.sp_off.ptr, self.sp_pts.ptr, d_sel.ptr, d_coff.ptr, d_boff.ptr, len(live), ntot, nmax, 0,
+                                                d_cen.ptr, d_dir.ptr, d_adj.ptr, st))
+        _lib.check(L.ssdr_select_set_chamfer_mode(self.chamfer_mode))
+        d_out = DevArray((picks,), np.int32)
+        _lib.check(L.ssdr_edcd_fps_batch_dev(d_cen.ptr, d_dir.ptr, d_coff.ptr, d_boff.ptr, d_ntop.ptr, len(live), nmax, picks, d_out.ptr, None, st))
+        self._keep = [d_sel, d_coff, d_boff, d_ntop, d_cen, d_dir, d_adj]
+        self._pending = (d_out, unl)
+
     @property
     def comb_all(self):
         """the gathered candidate features of the last sharded step (tests)"""
@@ -612,19 +733,34 @@ class HotPath:
             self._comb_dev, self._comb_n = V["d_glob"], n_g + (V["n_lab_all"] if self.selector == "kcenter" else 0)
             if V["rep"] > 1:
                 self._emu_mod = n_g
+        elif isinstance(d_out, str) and d_out == "topk":     # the top regions of the ranking (this rank's own): sel = arange
+            res = unl.to_host(self.sel_stream)
+            _lib.check(_lib.lib().ssdr_select_status(self.sel_stream, None))
+            loc = res[8:8 + int(res[0])].astype(np.int64)
+            sel = np.arange(len(loc), dtype=np.int32)
+            ccloud = self.sp_cloud_h[loc]
+            unl = _Pairs(ccloud, loc)
+            self.unl_cloud_ids = np.asarray(self.room_ids, np.int64)[ccloud]; self.unl_sp = loc - np.asarray(self.sp_base, np.int64)[ccloud]
         elif isinstance(d_out, str):                          # the device-side rule: counts, picks and the candidate list in one read-back
             T = self._sel_static
-            res = T["d_result"].to_host(self.sel_stream)     # waits for the selection stream alone
+            d_res, max_select = (T["d_result"], T["picks"]) if unl is None else unl      # (the edcd chains name their result buffer)
+            res = d_res.to_host(self.sel_stream)             # waits for the selection stream alone
             # from ~20 tiles per GPU on the chain's FPS / k-center is a cooperative launch: one that was not co-resident reports it here
             _lib.check(_lib.lib().ssdr_select_status(self.sel_stream, None))
+            if res[5] & ~3:
+                raise RuntimeError("edcd_sampling: %s (status %d): nothing was selected" % (
+                    "a cloud has more than 8192 candidates" if res[5] & 4 else "the picks do not fit the capacities", int(res[5])))
             if res[5]:
                 raise RuntimeError("gcn_fps_sampling: the candidate rule produced more rows than the capacities allow (status %d)" % int(res[5]))
             n_unl, picks = int(res[0]), int(res[4])
             sel = res[8:8 + picks].copy()
-            cand = res[8 + T["picks"]: 8 + T["picks"] + n_unl].astype(np.int64)
+            cand = res[8 + max_select: 8 + max_select + n_unl].astype(np.int64)
             ccloud = self.sp_cloud_h[cand]
             unl = _Pairs(ccloud, cand)                               # (20 000 candidates in one AL round: the tuples are built when somebody reads them)
             self.unl_cloud_ids = np.asarray(self.room_ids, np.int64)[ccloud]; self.unl_sp = cand - np.asarray(self.sp_base, np.int64)[ccloud]
+        elif isinstance(d_out, np.ndarray):                   # (decided on the host: the top of the host rule, a round without picks)
+            sel = d_out
+            _lib.check(_lib.lib().ssdr_select_status(self.sel_stream, None))
         else:
             sel = d_out.to_host(self.sel_stream)             # waits for the selection stream alone
             # a cooperative (multi-workgroup) FPS / k-center launch that was not co-resident reports it here instead of returning a wrong selection
