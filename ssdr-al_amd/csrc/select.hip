@@ -2247,6 +2247,8 @@ static int fps_like(const double* d_feat, size_t n, int D, const int32_t* d_alre
     SelState& Q = sst(s);
     // SURVEY 8d (F4 / F5): per pick n * D * 8 bytes of features + n * 8 of distances read and written (n = the capacity here: the count is the device's)
     ProfScope prof("fps_chain", s, (double)count * ((double)n * D * 8.0 + 16.0 * (double)n));
+    // which seeding kernel and which form of the chain this call takes: zero-work scopes inside "fps_chain" (tests/test_fps_paths.py reads them; nothing when profiling is off)
+    auto took = [s](const char* name) { ProfScope mark(name, s, 0.0); };
     int nb = grid_for((long)n, ctx().num_cu * 2);
     // seeded single-workgroup paths: kc_init takes a wave per row and its partial maxima are read once — as many workgroups as give every
     // wave a few rows (6 workgroups for 1400 rows left the kernel latency-bound at 0.57 ms)
@@ -2256,17 +2258,19 @@ static int fps_like(const double* d_feat, size_t n, int D, const int32_t* d_alre
     static const bool kc_tiled = [] { const char* e = getenv("SSDR_KC_TILED"); return !e || e[0] != '0'; }();      // (A/B: 0 keeps kc_init at every size)
     if (kc_tiled && d_already && na && D == 32 && (double)n * (double)na > 4.0e6) {       // the reference's own round: rows in registers, seeds through LDS, seed slices over blockIdx.y
         const int rb = (int)((n + 255) / 256), ys = (int)std::max<size_t>(1, std::min<size_t>((na + KT_SEEDS - 1) / KT_SEEDS, (size_t)std::max(1, 2 * ctx().num_cu / rb)));
+        took("fps_seed:kc_init_tiled");
         SSDR_HIP(hipMemsetAsync(Q.mind.p, 0x7f, 8 * n, s));                    // 0x7f7f...: a positive double above every squared distance
         hipLaunchKernelGGL(kc_init_tiled, dim3(rb, ys), dim3(256), 0, s, d_feat, (int)n, d_already, (int)na, Q.mind.as<unsigned long long>(), d_n);
         hipLaunchKernelGGL(kc_finish, dim3(nb), dim3(256), 0, s, Q.mind.as<unsigned long long>(), (int)n, p1, d_n);
         SSDR_HIP(hipGetLastError());
-    } else if (d_already && na) hipLaunchKernelGGL(kc_init, dim3(nb), dim3(256), 0, s, d_feat, (int)n, D, d_already, (int)na, Q.mind.as<double>(), p1, d_n);
-    else hipLaunchKernelGGL(fill_double, dim3(grid_for((long)n)), dim3(256), 0, s, Q.mind.as<double>(), (int)n, 1.0e10);   // fps_gcn_cpu.py:135
+    } else if (d_already && na) { took("fps_seed:kc_init"); hipLaunchKernelGGL(kc_init, dim3(nb), dim3(256), 0, s, d_feat, (int)n, D, d_already, (int)na, Q.mind.as<double>(), p1, d_n); }
+    else { took("fps_seed:fill"); hipLaunchKernelGGL(fill_double, dim3(grid_for((long)n)), dim3(256), 0, s, Q.mind.as<double>(), (int)n, 1.0e10); }   // fps_gcn_cpu.py:135
     const bool seeded = d_already && na;
     if (D == 32 && n <= 1536) {   // register-resident single workgroup
         const int fp = seeded ? 1 : 0;
         // (1024 threads — four waves per SIMD issue a float64 instruction every 5.5 cycles, the two of this form every 6.5, tools/micro/valu_rate.hip — with row tid in
         // registers and rows 1024.. in LDS was built and measured: 2.42 against 2.39 ms for the selection stage; the barrier over sixteen waves takes the gain back)
+        took(n <= 512 ? "fps_form:block_reg<1>" : n <= 1024 ? "fps_form:block_reg<2>" : "fps_form:block_reg<3>");
         if (n <= 512) hipLaunchKernelGGL((fps_block_reg<32, 1, 512>), dim3(1), dim3(512), 0, s, d_feat, (int)n, fp, start, use_sqrt, p1, nb, Q.mind.as<double>(), (int)count, d_out, d_n);
         else if (n <= 1024) hipLaunchKernelGGL((fps_block_reg<32, 2, 512>), dim3(1), dim3(512), 0, s, d_feat, (int)n, fp, start, use_sqrt, p1, nb, Q.mind.as<double>(), (int)count, d_out, d_n);
         else hipLaunchKernelGGL((fps_block_reg<32, 3, 512>), dim3(1), dim3(512), 0, s, d_feat, (int)n, fp, start, use_sqrt, p1, nb, Q.mind.as<double>(), (int)count, d_out, d_n);
@@ -2312,6 +2316,7 @@ static int fps_like(const double* d_feat, size_t n, int D, const int32_t* d_alre
     const bool coop_ok = false;
 #endif
     if (n <= 16384 && !coop_ok) {     // one CU sweeps the candidates faster than a launch per iteration costs
+        took(D == 32 ? "fps_form:block<32>" : "fps_form:block<0>");
         if (D == 32) hipLaunchKernelGGL((fps_block<32>), dim3(1), dim3(1024), 0, s, d_feat, (int)n, D, seeded ? 1 : 0, start, use_sqrt, p1, nb, Q.mind.as<double>(), (int)count, d_out, d_n);
         else hipLaunchKernelGGL((fps_block<0>), dim3(1), dim3(1024), 0, s, d_feat, (int)n, D, seeded ? 1 : 0, start, use_sqrt, p1, nb, Q.mind.as<double>(), (int)count, d_out, d_n);
         SSDR_HIP(hipGetLastError());
@@ -2336,6 +2341,7 @@ static int fps_like(const double* d_feat, size_t n, int D, const int32_t* d_alre
             SSDR_TRY(Q.vtmp.reserve(recb + 64));
             SSDR_HIP(hipMemsetAsync(Q.vtmp.p, 0, recb + 64, s));      // tags start at 0: no pick has that number; abort word
             a.part = Q.vtmp.as<Part>(); a.sync = reinterpret_cast<int*>(Q.vtmp.as<char>() + recb); a.G = G2;
+            took("fps_form:coop_wave");
             static const bool dbg_env = getenv("SSDR_FPS_DBG") != nullptr;
             if (dbg_env) {
                 static DevBuf dbgbuf; SSDR_TRY(dbgbuf.reserve(8 * 8 * 512)); SSDR_HIP(hipMemsetAsync(dbgbuf.p, 0, 8 * 8 * 512, s));
@@ -2364,6 +2370,7 @@ static int fps_like(const double* d_feat, size_t n, int D, const int32_t* d_alre
             SSDR_TRY(Q.vtmp.reserve(recb + 64));
             SSDR_HIP(hipMemsetAsync(Q.vtmp.p, 0, recb + 64, s));      // tags start at 0: no pick has that number; abort word
             a.part = Q.vtmp.as<Part>(); a.sync = reinterpret_cast<int*>(Q.vtmp.as<char>() + recb); a.G = G2;
+            took(lpr == 2 ? "fps_form:coop_split<2>" : "fps_form:coop_split<4>");
             static const bool dbg_env = getenv("SSDR_FPS_DBG") != nullptr;
             if (dbg_env) {
                 static DevBuf dbgbuf; SSDR_TRY(dbgbuf.reserve(8 * 8 * 512)); SSDR_HIP(hipMemsetAsync(dbgbuf.p, 0, 8 * 8 * 512, s));
@@ -2394,6 +2401,7 @@ static int fps_like(const double* d_feat, size_t n, int D, const int32_t* d_alre
                 (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fps_coop_sweep<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * FT_WORDS * 64);
                 (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fps_coop_sweep<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * FT_WORDS * 64); });
             a.part = Q.vtmp.as<Part>(); a.sync = sync2;
+            took(sweep == 1 ? "fps_form:coop_sweep_m1" : sweep == 2 ? "fps_form:coop_sweep_m2" : "fps_form:coop_sweep_m3");
             static const bool dbg_env = getenv("SSDR_FPS_DBG") != nullptr;
             if (dbg_env) {       // development: where a pick's time goes, per workgroup (wave 0's clock)
                 static DevBuf dbgbuf; SSDR_TRY(dbgbuf.reserve(8 * 8 * 64)); SSDR_HIP(hipMemsetAsync(dbgbuf.p, 0, 8 * 8 * 64, s));
@@ -2417,10 +2425,12 @@ static int fps_like(const double* d_feat, size_t n, int D, const int32_t* d_alre
             SSDR_HIP(hipMemsetAsync(part, 0, 8 * 2 * (size_t)G * FR_REC * 2, s));      // tags start at 0: no pick has that number
             static std::once_flag once2;
             std::call_once(once2, [] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fps_coop_tag), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * FT_WORDS * 128); });
+            took("fps_form:coop_tag");
             hipLaunchKernelGGL(fps_coop_tag, dim3(G), dim3(FR_NT), 4 * 2 * (size_t)G * FT_WORDS, s, a);
             SSDR_HIP(hipGetLastError());
             return coop.launched(s, G);
         }
+        took("fps_form:coop_reg");
         hipLaunchKernelGGL(fps_coop_reg, dim3(G), dim3(FR_NT), 8 * (size_t)G * FR_REC, s, a);
         SSDR_HIP(hipGetLastError());
         return coop.launched(s, G);
@@ -2431,11 +2441,13 @@ static int fps_like(const double* d_feat, size_t n, int D, const int32_t* d_alre
         Part* part = Q.vtmp.as<Part>(); int* sync = reinterpret_cast<int*>(part + 2 * G);
         SSDR_HIP(hipMemsetAsync(sync, 0, 16, s));
         FpsCoopArgs a{d_feat, (int)n, D, seeded ? 1 : 0, start, use_sqrt, p1, nb, Q.mind.as<double>(), (int)count, d_out, part, sync, G, Q.status.as<int>(), d_n};
+        took("fps_form:coop");
         hipLaunchKernelGGL(fps_coop, dim3(G), dim3(FC_NT), 0, s, a);
         SSDR_HIP(hipGetLastError());
         return coop.launched(s, G);
     }
 #endif
+    took("fps_form:step");
     for (size_t it = 0; it < count; ++it) {
         Part* pin = (it & 1) ? p0 : p1; Part* pout = (it & 1) ? p1 : p0;
         const bool last = it + 1 == count;
