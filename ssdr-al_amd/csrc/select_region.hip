@@ -3,19 +3,18 @@
 //   plain uncertainty (:783-806): the first batch_size regions of the ranking.
 //
 // edcd runs every cloud's chain in ONE launch, one workgroup per cloud: the counts come from the device (the candidate rule of select.hip, or the
-// caller), so the host reads nothing between the ranking and the picks.  The arithmetic is fps_superpoint's (select.hip) step for step — ed =
+// caller), so the host reads nothing between the ranking and the picks.  The arithmetic is fps_superpoint's (select_fps.hip) step for step — ed =
 // (dx*dx + dy*dy) + dz*dz, dist = ed + cd, running minima from 1e10, trigger row 0, arg-max with the lowest index among equal values (np.argmax) —
 // so the picks are index for index those of the single-cloud entry.  What differs is the layout: fps_superpoint reads cd(c, i) as dir[c][i] +
 // dir[i][c], a strided column read (one cache line per row per pick); here each block is symmetrised once (IEEE addition commutes: the same
 // sums) and a pick reads one contiguous row.  The running minima live in LDS (8 B per row: 64 KiB at the 8 192-row limit).
 #include "ssdr_internal.hpp"
+#include "select_fps.hpp"
 #include "select_region.hpp"
 #include <mutex>
 
 namespace ssdr {
 namespace {
-
-__device__ __forceinline__ bool rg_better(double v, int i, double bv, int bi) { return v > bv || (v == bv && i < bi); }     // np.argmax: first maximum
 
 // (value, index) arg-max over the wave, result in every lane (values are never NaN here)
 __device__ __forceinline__ void wave_argmax_pair(double& v, int& i) {
@@ -23,7 +22,7 @@ __device__ __forceinline__ void wave_argmax_pair(double& v, int& i) {
     for (int o = 32; o > 0; o >>= 1) {
         const double ov = __shfl_xor(v, o);
         const int oi = __shfl_xor(i, o);
-        if (rg_better(ov, oi, v, i)) { v = ov; i = oi; }
+        if (better(ov, oi, v, i)) { v = ov; i = oi; }
     }
 }
 
@@ -111,7 +110,7 @@ __global__ __launch_bounds__(NT) void edcd_fps_batch(const double* __restrict__ 
             const double dist = ed + row[i];
             double m = mind[i];
             if (dist < m) { m = dist; mind[i] = m; }
-            if (rg_better(m, i, bv, bi)) { bv = m; bi = i; }
+            if (better(m, i, bv, bi)) { bv = m; bi = i; }
         }
         wave_argmax_pair(bv, bi);
         if constexpr (NW == 1) {
@@ -121,7 +120,7 @@ __global__ __launch_bounds__(NT) void edcd_fps_batch(const double* __restrict__ 
             __syncthreads();
             double v = s_v[0]; int k = s_i[0];
 #pragma unroll
-            for (int q = 1; q < NW; ++q) if (rg_better(s_v[q], s_i[q], v, k)) { v = s_v[q]; k = s_i[q]; }
+            for (int q = 1; q < NW; ++q) if (better(s_v[q], s_i[q], v, k)) { v = s_v[q]; k = s_i[q]; }
             c = k;
             __syncthreads();                 // s_v / s_i are rewritten by the next pick
         }

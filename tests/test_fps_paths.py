@@ -1,6 +1,6 @@
 """Farthest-point sampling and k-center greedy, launcher branch by launcher branch, against the float64 oracle (oracle/select_np.py).
 
-fps_like() (csrc/select.hip) picks one of eleven kernels and one of three seedings from (D, n, seeded, environment); a wrong pick still returns
+fps_like() (csrc/select_fps.hip) picks one of eleven kernels and one of three seedings from (D, n, seeded, environment); a wrong pick still returns
 `count` plausible indices.  It names what it took in two zero-work profiler scopes inside "fps_chain" ("fps_form:*", "fps_seed:*").  Every case here
 runs through the C ABI (ssdr_fps_dev: squared distances; ssdr_kcenter_dev: their square roots, seeded by kc_init / kc_init_tiled), must equal
 oracle.select_np.farthest_features_sample / kcenter_greedy INDEX FOR INDEX, must leave ssdr_select_status at 0 with no pick of -1, and must report
@@ -362,10 +362,10 @@ def test_replay_equals_the_oracle():
 
 
 def test_cases_cover_every_form_and_seeding():
-    """Every "fps_form:" / "fps_seed:" name of select.hip is reached by a case that asserts it at run time (the default dispatch above, the environment
+    """Every "fps_form:" / "fps_seed:" name of select_fps.hip is reached by a case that asserts it at run time (the default dispatch above, the environment
     rows, the live-count cases).  One exception: fps_block<32> runs on the GPU only when the occupancy query refuses the cooperative grid, which no test
     may force; it counts as covered by the CPU logic build's cases (every D = 32 case of 1537 .. 16 384 rows takes it there)."""
-    src = open(os.path.join(ROOT, "ssdr-al_amd", "csrc", "select.hip")).read()
+    src = open(os.path.join(ROOT, "ssdr-al_amd", "csrc", "select_fps.hip")).read()
     names = set(re.findall(r'"(fps_(?:form|seed):[^"]+)"', src))
     assert len(names) >= 17, sorted(names)
     gpu = {r for c in CASES for r in c.reach} | {"fps_form:" + form for _, _, sizes in ENV_ROWS for _, _, form, _ in sizes} | \

@@ -425,7 +425,7 @@ def test_cooperative_fps_reports_a_launch_that_is_not_co_resident():
 def test_cooperative_chains_in_flight_on_several_streams(budget):
     """Three cooperative chains on three streams enqueued back to back (`--select-lag 2` keeps three global chains in flight): every launch is
     sized against the co-resident workgroups, so their SUM must fit as well — the library keeps an account of the cooperative grids in
-    flight and makes a launch's stream wait for the oldest ones when it would not (select.hip: coop_admit).  With the default budget and with a
+    flight and makes a launch's stream wait for the oldest ones when it would not (select_fps.hip: CoopGuard).  With the default budget and with a
     budget of one chain's grid (full serialisation, SSDR_FPS_COOP_BUDGET) all three give the reference's sequences and no stream reports an abort."""
     from conftest import GPU_LIB, _have_gpu
     if not _have_gpu():
