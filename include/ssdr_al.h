@@ -445,6 +445,35 @@ int ssdr_edcd_sampling_sharded_dev(const float* d_xyz, const int32_t* d_sp_off, 
  * d_skip[id] == 0, in rank order; of them, the ids in [lo, hi) are written to d_out as id - lo (a sharded rank keeps its own: lo = rank * Smax).
  * d_res[0] = entries written, d_res[1] = the size of the whole top.  d_out holds min(batch_size, hi - lo). */
 int ssdr_topk_regions_dev(const int32_t* d_order, size_t n, const uint8_t* d_skip, size_t batch_size, size_t lo, size_t hi, int32_t* d_res, int32_t* d_out, void* stream);
+/* ---- oracle_labeling (sampler2.py:124-192) over the picks of one round, in the order sampling() calls _help() (:676-684, :796-806) ---------------
+ * Enqueue-only.  d_items [max_items]: the picked regions as global superpoint ids in pick order, *d_n_items (device) of them are live; items are grouped by
+ * cloud (d_sp_cloud [S], values below num_clouds), the clouds ordered by d_cloud_key [num_clouds] (NULL: first appearance among the items), a cloud's
+ * picks in pick order.  The walk over that list is the reference's: stop at click <= 0, skip regions of fewer than min_size points at no cost, otherwise
+ * pay one click and label the region with its dominant ground-truth label d_gt (lowest label among equals) — SSDR_LABEL_DOMINANT always, SSDR_LABEL_NAIL
+ * when count / len >= threshold (float64); else the points split by predicted class d_pred_class, every sub-region of MORE than min_size points whose own
+ * rate reaches the threshold pays one more click and is labelled (the budget may end below zero).  num_labels <= 64, num_classes <= 32; labels / classes /
+ * ids outside their range are not counted and raise a status bit.  max_region: an upper bound of a region's size when the caller knows one (0: unknown) —
+ * regions of up to 256 points are judged by a wave each, larger ones by a workgroup, and the workgroup kernels are not launched when none can occur.
+ * In place: d_mask / d_label [n] float32 (the two rows of pseudo_gt), d_labeled [S] uint8, *d_budget (int64, the clicks left).  Written: d_used
+ * [max_items] uint8 per item (pick order), d_class_out [class_cap] the appended selected_class_list entries in the reference's order, d_proc_order
+ * (optional, [max_items]) the item processed at every position of the walk, d_out int64 [12]: sp_num, p_num, sub_num, sub_p_num, split_sp_num,
+ * ignore_sp_num, class entries, budget left, status (1: label, 2: class out of range, 4: item / point id out of range, 8: more entries than class_cap:
+ * the class list is incomplete), items used, regions judged by the wave form, by the workgroup form. */
+#define SSDR_LABEL_DOMINANT 0
+#define SSDR_LABEL_NAIL     1
+int ssdr_oracle_label_dev(const int32_t* d_gt, const int32_t* d_pred_class, size_t n, const int32_t* d_sp_off, const int32_t* d_sp_pts, size_t S,
+                          const int32_t* d_sp_cloud, size_t num_clouds, const int32_t* d_items, const int32_t* d_n_items, size_t max_items,
+                          const int32_t* d_cloud_key, size_t max_region, int num_labels, int num_classes, int mode, double threshold, int64_t min_size,
+                          int64_t* d_budget, float* d_mask, float* d_label, uint8_t* d_used, uint8_t* d_labeled, int32_t* d_class_out, size_t class_cap,
+                          int32_t* d_proc_order, int64_t* d_out, void* stream);
+/* The picks of a one-call selection as the item list above, on the device: d_result of ssdr_gcn_fps_sampling_dev / ssdr_edcd_sampling_dev (layout 0:
+ * picks at word 8 index the candidate list at word 8 + max_select, counts in words 0 and 4, nothing when the status word 5 is set) or of
+ * ssdr_topk_regions_dev (layout 1: d_res with d_out = d_res + 8; max_select = max_items).  d_result NULL: the items are the caller's.  d_cloud_key
+ * (optional, [num_clouds]): every cloud's first place in the ranking d_order [S] among the regions with d_skip == 0 — the edcd round's cloud order
+ * (file_list_top, sampler2.py:533-552). */
+int ssdr_oracle_label_items_dev(const int32_t* d_result, int layout, size_t max_select, const int32_t* d_order, size_t S, const uint8_t* d_skip,
+                                const int32_t* d_sp_cloud, size_t num_clouds, int32_t* d_items, size_t max_items, int32_t* d_n_items, int32_t* d_cloud_key,
+                                void* stream);
 /* kCenterGreedy.select_batch_ (kcenterGreedy.py:84-128) with direct float64 Euclidean distances */
 int ssdr_kcenter_dev(const double* d_feat, size_t n, int feat_dim, const int32_t* d_already_selected, size_t n_already, size_t count,
                      int32_t* d_out, void* stream);

@@ -106,6 +106,8 @@ def lib():
         L.ssdr_edcd_sampling_dev.argtypes = [vp, vp, vp, vp, sz, vp, vp, sz, sz, sz, sz, sz, sz, vp, vp]
         L.ssdr_edcd_sampling_sharded_dev.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, i32, i32, sz, sz, sz, sz, sz, sz, sz, vp, vp]
         L.ssdr_topk_regions_dev.argtypes = [vp, sz, vp, sz, sz, sz, vp, vp, vp]
+        L.ssdr_oracle_label_dev.argtypes = [vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, sz, vp, sz, i32, i32, i32, f64, C.c_int64, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]
+        L.ssdr_oracle_label_items_dev.argtypes = [vp, i32, sz, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp]
         L.ssdr_gcn_fps_sharded_local_dev.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, i32, i32, sz, sz, sz, i32, i32, sz, sz, sz, sz, sz, vp, vp, vp]
         L.ssdr_event_create.argtypes = [C.POINTER(vp)]; L.ssdr_event_record.argtypes = [vp, vp]; L.ssdr_stream_wait_event.argtypes = [vp, vp]; L.ssdr_event_destroy.argtypes = [vp]
         L.ssdr_select_set_chamfer_mode.argtypes = [i32]

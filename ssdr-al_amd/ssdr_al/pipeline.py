@@ -101,6 +101,8 @@ class HotPath:
         self.global_order = None
         self.rooms = []
         self.timing = None
+        self.pt_off = None          # where every cloud's points start in the concatenated arrays (LabelResult.to_host per cloud)
+        self.pseudo_mask = self.pseudo_label = None      # the two rows of pseudo_gt over all points, resident across rounds (label_selected)
 
     # ---- setup (untimed): upload raw rooms, fix the per-room randomness, derive superpoints -------------------
     def draw_room(self, xyz, rid):
@@ -176,6 +178,7 @@ class HotPath:
             rng = np.random.default_rng([self.seed, self.room_ids[b], 1])
             labeled[b] = set(rng.choice(ids, min(self.labeled_per_tile, len(ids)), replace=False).tolist())
         self.n_pts = B * N
+        self.pt_off = np.arange(B + 1, dtype=np.int64) * N
         self._set_regions(np.concatenate(offs), np.concatenate(pts), sp_cloud, labeled,
                           np.random.default_rng([self.seed, 999983]).integers(0, cfg.num_classes, 4000))
         return self
@@ -193,11 +196,13 @@ class HotPath:
             o = np.asarray(c["offsets"], np.int64)
             offs.append(o[1:] + offs[-1][-1]); pts.append(np.asarray(c["points"], np.int64) + p0[b]); cloud.append(np.full(len(o) - 1, b, np.int32))
             lab[b] = set(int(s) + s0 for s in labeled[b]); s0 += len(o) - 1
-        return cls.from_device(DevArray.from_host(np.concatenate([np.asarray(c["xyz"], np.float32) for c in clouds])),
+        hp = cls.from_device(DevArray.from_host(np.concatenate([np.asarray(c["xyz"], np.float32) for c in clouds])),
                                DevArray.from_host(np.concatenate([np.asarray(c["probs"], np.float32) for c in clouds])),
                                DevArray.from_host(np.concatenate([np.asarray(c["feat"], np.float32) for c in clouds])),
                                DevArray.from_host(np.concatenate([np.asarray(c["gt"]).astype(np.int32) for c in clouds])),
                                np.concatenate(offs), np.concatenate(pts), np.concatenate(cloud), lab, selected_class_list, config, room_ids=room_ids, **kw)
+        hp.pt_off = p0
+        return hp
 
     @classmethod
     def from_device(cls, xyz, probs, f32, labels, sp_off, sp_pts, sp_cloud, labeled, selected_class_list, config=ConfigS3DIS, room_ids=None, **kw):
@@ -229,10 +234,12 @@ class HotPath:
         self.S = len(self.sp_off_h) - 1
         self.sp_base = np.searchsorted(self.sp_cloud_h, np.arange(B)).astype(np.int64).tolist()      # (clouds are ascending: every cloud owns at least one region)
         self.sp_off = DevArray.from_host(self.sp_off_h); self.sp_pts = DevArray.from_host(self.sp_pts_h)
+        self.d_sp_cloud = DevArray.from_host(self.sp_cloud_h if self.S else np.zeros(1, np.int32))
         self.region_unc = DevArray((self.S,), np.float64); self.dom = DevArray((self.S,), np.int32); self.dom_cnt = DevArray((self.S,), np.int32)
         self.gt_dom = DevArray((self.S,), np.int32); self.gt_purity = DevArray((self.S,), np.float64)
         self.sorted_inds = DevArray((self.S,), np.int32)
-        self.selected_class_list = DevArray.from_host(np.asarray(selected_class_list).astype(np.int32).reshape(-1))
+        self._class_list_h = np.asarray(selected_class_list).astype(np.int32).reshape(-1)      # host mirror: label_selected appends to both
+        self.selected_class_list = DevArray.from_host(self._class_list_h)
         self.hist = DevArray((64,), np.int32)
         self.sp_size_h = np.diff(self.sp_off_h)
         self.set_labeled(labeled)
@@ -487,6 +494,7 @@ class HotPath:
 
     def _select_issue(self, comm=None):
         """everything of the selection up to the enqueued FPS chain (the host decisions and uploads happen here)"""
+        self._last_comm = comm
         if self.selector in ("edcd", "topk"):
             return self._select_issue_region(comm)
         L = _lib.lib()
@@ -733,7 +741,9 @@ class HotPath:
             self._comb_dev, self._comb_n = V["d_glob"], n_g + (V["n_lab_all"] if self.selector == "kcenter" else 0)
             if V["rep"] > 1:
                 self._emu_mod = n_g
+            where = None
         elif isinstance(d_out, str) and d_out == "topk":     # the top regions of the ranking (this rank's own): sel = arange
+            where = dict(layout=1, buf=unl, max_select=int(unl.shape[0]) - 8)
             res = unl.to_host(self.sel_stream)
             _lib.check(_lib.lib().ssdr_select_status(self.sel_stream, None))
             loc = res[8:8 + int(res[0])].astype(np.int64)
@@ -744,6 +754,7 @@ class HotPath:
         elif isinstance(d_out, str):                          # the device-side rule: counts, picks and the candidate list in one read-back
             T = self._sel_static
             d_res, max_select = (T["d_result"], T["picks"]) if unl is None else unl      # (the edcd chains name their result buffer)
+            where = dict(layout=0, buf=d_res, max_select=int(max_select))
             res = d_res.to_host(self.sel_stream)             # waits for the selection stream alone
             # from ~20 tiles per GPU on the chain's FPS / k-center is a cooperative launch: one that was not co-resident reports it here
             _lib.check(_lib.lib().ssdr_select_status(self.sel_stream, None))
@@ -760,8 +771,10 @@ class HotPath:
             self.unl_cloud_ids = np.asarray(self.room_ids, np.int64)[ccloud]; self.unl_sp = cand - np.asarray(self.sp_base, np.int64)[ccloud]
         elif isinstance(d_out, np.ndarray):                   # (decided on the host: the top of the host rule, a round without picks)
             sel = d_out
+            where = "host"
             _lib.check(_lib.lib().ssdr_select_status(self.sel_stream, None))
         else:
+            where = "host"
             sel = d_out.to_host(self.sel_stream)             # waits for the selection stream alone
             # a cooperative (multi-workgroup) FPS / k-center launch that was not co-resident reports it here instead of returning a wrong selection
             _lib.check(_lib.lib().ssdr_select_status(self.sel_stream, None))
@@ -777,6 +790,12 @@ class HotPath:
         if getattr(self, "_emu_mod", 0):                    # (SSDR_EMULATE_WORLD: the picks index the repeated rows)
             sel = sel % self._emu_mod
         si = np.asarray(sel, np.int64)
+        if where == "host" and getattr(self, "_last_comm", None) is not None:
+            where = None             # (a sharded round: sel indexes all ranks' candidates, unl is this rank's share; label_selected refuses it anyway)
+        if where == "host":          # decided on the host: the picks as global region ids (label_selected uploads them)
+            ids = unl.b if isinstance(unl, _Pairs) else np.asarray([u[1] for u in unl], np.int64)
+            where = dict(layout=None, items=np.asarray(ids, np.int64).reshape(-1)[si])
+        self._last_sel = where      # where the picks of this selection lie, for label_selected (None: a sharded round)
         self._selected = _Pairs(np.asarray(self.unl_cloud_ids)[si], np.asarray(self.unl_sp)[si])      # (room id, superpoint in room)
         return sel, unl
 
@@ -789,6 +808,73 @@ class HotPath:
     @selected.setter
     def selected(self, value):
         self._selected = value
+
+    # ---- the oracle: pseudo labels for the picks of the last selection (sampler2.py:124-216) ------------------
+    def set_pseudo_gt(self, pseudo_gt):
+        """the resident pseudo labels' content: [2, n] over all points (row 0 labelled flag, row 1 label), or one [2, n_c] array per cloud"""
+        a = np.concatenate([np.asarray(p, np.float32) for p in pseudo_gt], axis=1) if isinstance(pseudo_gt, (list, tuple)) else np.asarray(pseudo_gt, np.float32)
+        assert a.shape == (2, self.n_pts), "pseudo_gt must be [2, %d]" % self.n_pts
+        self.pseudo_mask, self.pseudo_label = DevArray.from_host(np.ascontiguousarray(a[0])), DevArray.from_host(np.ascontiguousarray(a[1]))
+        return self
+
+    def label_selected(self, mode="NAIL", threshold=0.9, min_size=None, budget=None):
+        """_help() / oracle_labeling() for every cloud that received picks (sampler2.py:124-216, called from sampling() :676-684, :775-781, :796-806), on
+        the device and from the device buffers of the last selection: the picks become pseudo labels while the click budget (default: the round's
+        batch_size, as sampling() sets it) lasts.  Afterwards self.labeled, the skip mask and selected_class_list are what set_labeled() would
+        produce for the next round: step_selection() can be called again.  Returns a LabelResult."""
+        from . import sampler
+        if getattr(self, "_last_comm", None) is not None:
+            raise ValueError("label_selected: the last selection ran with a communicator; the budget walk is global over all ranks' picks and a sharded "
+                             "labelling is not offered")
+        where = getattr(self, "_last_sel", None)
+        if where is None:
+            raise RuntimeError("label_selected: no selection to label (run step_selection() / step() first)")
+        L, st, T = _lib.lib(), self.sel_stream, self._sel_static
+        m = sampler.label_mode([mode] if isinstance(mode, str) else mode)
+        batch = int(T["batch"])
+        budget = batch if budget is None else int(budget)
+        min_size = self.min_size if min_size is None else int(min_size)
+        if self.pseudo_mask is None:
+            self.set_pseudo_gt(np.zeros((2, self.n_pts), np.float32))
+        edcd = self.selector == "edcd"
+        d_key = DevArray((max(self.B, 1),), np.int32) if edcd else None
+        if where["layout"] is None:
+            items = where["items"]
+            M = len(items)
+            d_items = DevArray.from_host(np.concatenate([items, [0]]).astype(np.int32), st); d_n = DevArray.from_host(np.array([M], np.int32), st)
+            if edcd:
+                _lib.check(L.ssdr_oracle_label_items_dev(None, 0, 0, self.sorted_inds.ptr, self.S, T["d_lab"].ptr, self.d_sp_cloud.ptr, self.B, None, 0, None, d_key.ptr, st))
+        else:
+            M = int(where["max_select"])
+            d_items = DevArray((max(M, 1),), np.int32); d_n = DevArray((1,), np.int32)
+            _lib.check(L.ssdr_oracle_label_items_dev(where["buf"].ptr, where["layout"], M, self.sorted_inds.ptr if edcd else None, self.S, T["d_lab"].ptr,
+                                                     self.d_sp_cloud.ptr, self.B, d_items.ptr, M, d_n.ptr, d_key.ptr if edcd else None, st))
+        nc = int(self.cfg.num_classes)
+        cap = max(1, min(M * nc, max(budget, 0) + nc + 1))
+        d_budget = DevArray.from_host(np.array([budget], np.int64), st)
+        d_used, d_proc = DevArray((max(M, 1),), np.uint8), DevArray((max(M, 1),), np.int32)
+        d_labeled = DevArray.from_host(self.labeled_mask.astype(np.uint8) if self.S else np.zeros(1, np.uint8), st)
+        d_cls, d_out = DevArray((cap,), np.int32), DevArray((12,), np.int64)
+        _lib.check(L.ssdr_oracle_label_dev(self.tile_l.ptr, self.cls.ptr, self.n_pts, self.sp_off.ptr, self.sp_pts.ptr, self.S, self.d_sp_cloud.ptr, self.B,
+                                           d_items.ptr, d_n.ptr, M, d_key.ptr if edcd else None, int(self.sp_size_h.max()) if self.S else 1, max(nc, 1), nc, m,
+                                           float(threshold), min_size, d_budget.ptr, self.pseudo_mask.ptr, self.pseudo_label.ptr, d_used.ptr, d_labeled.ptr,
+                                           d_cls.ptr, cap, d_proc.ptr, d_out.ptr, st))
+        out = d_out.to_host(st)                              # waits for the selection stream alone
+        sampler.label_status_check(int(out[8]))
+        used_f, proc = d_used.to_host(st), d_proc.to_host(st)
+        n_items = int(d_n.to_host(st)[0])
+        proc = proc[:n_items]
+        upos = proc[used_f[proc] != 0]                       # the used picks in the order the walk met them
+        sel_pairs = self.__dict__.get("_selected")
+        used = _Pairs(np.asarray(sel_pairs.a)[upos], np.asarray(sel_pairs.b)[upos])
+        entries = d_cls.to_host(st)[: int(out[6])]
+        self._class_list_h = np.concatenate([self._class_list_h, entries]).astype(np.int32)
+        self.selected_class_list = DevArray.from_host(self._class_list_h)
+        mask = d_labeled.to_host(st)[: self.S] != 0
+        self.set_labeled({b: set(np.flatnonzero(mask & (self.sp_cloud_h == b)).tolist()) for b in range(self.B)})
+        self._last_sel = None                                # (these picks are spent)
+        return LabelResult(self, dict(zip(sampler.LABEL_COUNTERS, (int(x) for x in out[:6]))), int(out[7]), used, entries,
+                           dict(wave=int(out[10]), block=int(out[11])))
 
     def step(self, comm=None, timed_stages=False):
         """One pass of the hot path over the loaded batch of rooms.  Returns the selected candidate indices."""
@@ -805,6 +891,28 @@ class HotPath:
         if timed_stages:
             self.timing = dict(zip(("subsample+tile", "knn_pyramid", "randla_infer", "score", "select"), np.diff(t) * 1e3))
         return out
+
+
+class LabelResult:
+    """What HotPath.label_selected / ALRound.label hand back: `mask` / `label` (device, float32 [n]: the two rows of pseudo_gt over all points, the
+    HotPath's own resident arrays), `used` as (room id, superpoint in room) pairs in the order the walk met them, the six `counters` of the
+    reference's `w`, `budget_left` (may be negative), `class_entries` appended to selected_class_list, `forms`: regions judged per kernel form."""
+    def __init__(self, hp, counters, budget_left, used, class_entries, forms):
+        self._hp, self.mask, self.label = hp, hp.pseudo_mask, hp.pseudo_label
+        self.counters, self.budget_left, self._used, self.class_entries, self.forms = counters, budget_left, used, class_entries, forms
+
+    @property
+    def used(self):
+        return self._used.tolist()
+
+    def to_host(self, cloud=None):
+        """pseudo_gt as io_formats.save_gt writes it: float32 [2, n_c] of one cloud (None: [2, n] over all points)"""
+        both = np.stack([self.mask.to_host(self._hp.sel_stream), self.label.to_host(self._hp.sel_stream)])
+        if cloud is None:
+            return both
+        if self._hp.pt_off is None:
+            raise ValueError("to_host(cloud): the HotPath does not know where its clouds' points start (set pt_off)")
+        return np.ascontiguousarray(both[:, int(self._hp.pt_off[cloud]): int(self._hp.pt_off[cloud + 1])])
 
 
 class _Rows:
@@ -898,6 +1006,7 @@ class ALRound:
                                        config, batch_size=batch_size, round_num=round_num, selector=selector, gcn_number=gcn_number, gcn_top=gcn_top, min_size=min_size, seed=seed)
         self.sel.stream = self.sel.score_stream = self.sel.sel_stream = s_i
         self.sel.front_stream = s_i; self.sel.pipelined = True
+        self.sel.pt_off = np.arange(self.tiles + 1, dtype=np.int64) * N
         self.tile_points = P
 
     def _bind(self, b):
@@ -955,6 +1064,11 @@ class ALRound:
             _lib.check(_lib.lib().ssdr_grid_subsample_status(st, None))
         _lib.check(_lib.lib().ssdr_grid_subsample_status(self.s_front, None))
         return out
+
+    def label(self, mode="NAIL", threshold=0.9, min_size=None, budget=None):
+        """the oracle over the round's picks (HotPath.label_selected on the round's arrays): the labelled set, the class list and the pseudo labels
+        are then those of the next round"""
+        return self.sel.label_selected(mode=mode, threshold=threshold, min_size=min_size, budget=budget)
 
 
 class BatchStreams:

@@ -64,6 +64,62 @@ def dominant_labels(labels, offsets, points, num_labels):
     return d_lab.to_host(), d_pur.to_host()
 
 
+LABEL_COUNTERS = ("sp_num", "p_num", "sub_num", "sub_p_num", "split_sp_num", "ignore_sp_num")
+LABEL_STATUS = ((1, "a ground-truth label outside [0, num_labels)"), (2, "a predicted class outside [0, num_classes)"),
+                (4, "a region or point id outside the arrays"), (8, "more class entries than the class list holds"))
+
+
+def label_mode(sampler_args):
+    """the oracle mode a reference `sampler_args` names, tested in the reference's order (sampler2.py:127, :146); -1: none (the library refuses it)"""
+    args = [sampler_args] if isinstance(sampler_args, str) else list(sampler_args)
+    return 0 if "dominant" in args else 1 if "NAIL" in args else -1
+
+
+def label_status_check(status):
+    if status:
+        raise ValueError("oracle_label: " + "; ".join(msg for bit, msg in LABEL_STATUS if status & bit) + " (status %d)" % status)
+
+
+def oracle_labeling(superpoint_inds, components, input_gt, pseudo_gt, cloud_name, w, sampler_args, prob_class, threshold, budget, min_size, total_obj,
+                    num_labels=64, num_classes=32):
+    """sampler2.py:124-192 for one cloud through ssdr_oracle_label_dev: walks `superpoint_inds` while budget["click"] lasts, writes the two rows of
+    `pseudo_gt` ([2, n]: labelled flag, pseudo label), appends to total_obj["selected_class_list"], adds to the counters in `w`, takes the clicks from
+    `budget`; returns (pseudo_gt, used_superpoint_inds).  sampler_args names the mode ("dominant" or "NAIL"); prob_class [n] are the predicted classes
+    (NAIL).  Labels go up to num_labels - 1 <= 63, classes up to num_classes - 1 <= 31."""
+    inds = np.asarray(list(superpoint_inds), np.int64).reshape(-1)
+    off, pts = csr_from_components(components)
+    gt = np.ascontiguousarray(np.asarray(input_gt).reshape(-1), np.int32)
+    n, S, M = len(gt), len(off) - 1, len(inds)
+    mode = label_mode(sampler_args)
+    m0 = np.ascontiguousarray(np.asarray(pseudo_gt[0]), np.float32); l0 = np.ascontiguousarray(np.asarray(pseudo_gt[1]), np.float32)
+    d_gt = DevArray.from_host(gt)
+    d_pred = None if prob_class is None else DevArray.from_host(np.ascontiguousarray(np.asarray(prob_class).reshape(-1), np.int32))
+    d_off, d_pts = DevArray.from_host(off), DevArray.from_host(pts)
+    d_cloud = DevArray.from_host(np.zeros(max(S, 1), np.int32))
+    d_items = DevArray.from_host(np.concatenate([inds, [0]]).astype(np.int32)); d_n = DevArray.from_host(np.array([M], np.int32))
+    d_budget = DevArray.from_host(np.array([int(budget["click"])], np.int64))
+    d_m, d_l = DevArray.from_host(m0), DevArray.from_host(l0)
+    d_used = DevArray((max(M, 1),), np.uint8); d_lab = DevArray.from_host(np.zeros(max(S, 1), np.uint8))
+    cap = max(1, min(M * 32, max(int(budget["click"]), 0) + 33))
+    d_cls = DevArray((cap,), np.int32); d_out = DevArray((12,), np.int64)
+    _lib.check(_lib.lib().ssdr_oracle_label_dev(d_gt.ptr, d_pred.ptr if d_pred is not None else None, n, d_off.ptr, d_pts.ptr, S, d_cloud.ptr, 1, d_items.ptr,
+                                                d_n.ptr, M, None, int(np.diff(off).max()) if S else 1, int(num_labels), int(num_classes), mode, float(threshold),
+                                                int(min_size), d_budget.ptr, d_m.ptr, d_l.ptr, d_used.ptr, d_lab.ptr, d_cls.ptr, cap, None, d_out.ptr, None))
+    _lib.sync()
+    out = d_out.to_host()
+    label_status_check(int(out[8]))
+    m1, l1 = d_m.to_host(), d_l.to_host()
+    ch = np.flatnonzero((m1 != m0) | (l1 != l0))          # (points the walk did not write keep the caller's values, whatever their type)
+    pseudo_gt[0][ch] = m1[ch]; pseudo_gt[1][ch] = l1[ch]
+    for k, name in enumerate(LABEL_COUNTERS):
+        if out[k] or name in w:
+            w[name] = w.get(name, 0) + int(out[k])
+    budget["click"] = int(out[7])
+    total_obj.setdefault("selected_class_list", []).extend(d_cls.to_host()[: int(out[6])].tolist())
+    used = d_used.to_host()[:M]
+    return pseudo_gt, [superpoint_inds[i] for i in np.flatnonzero(used)]
+
+
 def add_clsbal(class_num, region_class, region_uncertainty, total_obj, skip=None):
     """sampler2.py:262-266.  The reference passes the UNLABELLED regions only (prediction(), :612-627); a caller that keeps every region in
     one array marks the others in `skip` (non-zero: not part of the population)."""
