@@ -359,6 +359,69 @@ int ssdr_propagate_dev(const double* d_adj, size_t n, const int32_t* d_rows, con
  * every member in the result (the reference's ref_idx: unlabelled candidates first, then the labelled regions).  N <= 32767. */
 int ssdr_create_adj_dev(const float* d_feat, size_t N, int F, const double* d_centres, const double* d_cd_dir, const int32_t* d_coff, const int64_t* d_boff,
                         size_t num_clouds, size_t n_max, const int32_t* d_rows, float* d_out_v, float* d_out_adj, void* stream);
+/* ---- the trained-GCN selector: gcn.GCN_sampling (S3/gcn.py:193-263; sampler2.py's "gcn" branch, :687-734), csrc/select_gcn.hip ----------------
+ * The graph is the one of ssdr_cloud_graph_batch_dev: cloud c owns the grouped positions d_coff[c] .. d_coff[c+1]-1 and the n_c x n_c block at d_boff[c];
+ * d_rows [rows] names, cloud by cloud, the row of every member in the reference's [unlabelled | labelled] order (ref_idx).  d_counts (device int32,
+ * the first words of a one-call chain's d_result): [0] unlabelled rows, [1] labelled rows, [2] rows in all — the LIVE counts every kernel reads;
+ * cap_rows / n_max (>= rows / >= the largest block) only shape the launches, rows beyond the live count are never read.
+ * d_info (device int32 [8]): [0] status bits below, [1] the first cloud with a single row (0x7fffffff: none), [2] values substituted by the
+ * evaluation, [3] the training form that ran.  ssdr_gcn_block_adj_dev resets it; the others add to it.
+ *
+ * ssdr_gcn_block_adj_dev: gcn.create_adj (gcn.py:177-189) stored as per-cloud blocks and never as the [N,N] matrix: d_feat [rows,32] ->
+ * d_out_v (rows L2-normalised, eps 1e-12); block[i][j] = <v_i, v_j> * exp(-((float)ED + (float)CD)) - (i == j), columns scaled by the inverse of their
+ * float32 sums, plus I -> d_out_adj; d_out_adjT holds every block transposed (bit for bit); d_rowcloud [cap_rows] the cloud of every grouped position.
+ * Inside a block the values are ssdr_create_adj_dev's.  A cloud that contributes ONE row has the column sum 0 (the reference divides by it and trains on
+ * NaN): SSDR_GCN_ST_SINGLETON is raised, the block is left as the identity, and training / evaluation do nothing.
+ *
+ * ssdr_gcn_train_dev: `steps` Adam steps of the reference's GCN (gcn.py:60-86, :207-226; nfeat 32, nhid 128; gc2 and linear never receive a gradient and
+ * are not represented):  h = A (V W1) + b1;  feat = dropout_p(relu(h)) (kept values times 1 / (1 - p));  x = A (feat W3) + b3;  s = sigmoid(x);
+ * loss = -mean(log s[labelled]) - lamda * mean(log(1 - s[unlabelled]));  torch.optim.Adam(lr, betas (0.9, 0.999), eps 1e-8, weight_decay): the decay is
+ * added to the gradient, denom = sqrt(v) / sqrt(1 - beta2^t) + eps, step size lr / (1 - beta1^t).  Parameters are one float32 array of
+ * SSDR_GCN_NPARAM values: W1 [32,128] row-major, b1 [128], W3 [128], b3.  d_init -> d_trained (may be the same array); d_loss [2] = the loss of step 0's
+ * forward pass (with its dropout) and the loss after the last step (forward pass without dropout).  No labelled row (d_counts[1] == 0; the loss is a
+ * mean over an empty set): SSDR_GCN_ST_NO_LABELLED, nothing is trained.  Without unlabelled rows the second term is 0.
+ * Dropout: unit k of the row r (its index in the [unlabelled | labelled] order) is KEPT at step t (0-based) iff
+ *     z = seed + 0x9E3779B97F4A7C15 * (t + 1) + 0xD6E8FEB86659FD93 * (128 r + k + 1)                      (all mod 2^64)
+ *     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^= z >> 31
+ *     (float)(z >> 40) * 2^-24 >= p                                                                       (float32 comparison)
+ * — a function of (seed, step, row, unit) alone, whatever the launch geometry.
+ * form: SSDR_GCN_FORM_GENERAL (row-parallel launches, any block size), SSDR_GCN_FORM_FUSED (a workgroup owns whole clouds; n_max <=
+ * SSDR_GCN_FUSED_CAP or SSDR_ERR_INVALID), SSDR_GCN_FORM_AUTO (fused when n_max allows it).  The gradient sums are float64 in a fixed order: the same
+ * call twice gives the same bits.  The two forms agree to float32 rounding, not bit for bit.
+ *
+ * ssdr_gcn_eval_dev: the evaluation pass (gcn.py:230-245) -> d_out [cap_rows,129] float64, row r = cat(relu(h_r), x_r) without dropout, NaN replaced
+ * by 1e-10 and +-inf by 1e10 (d_info[2] counts them, SSDR_GCN_ST_SUBSTITUTED).  After a refusal the live rows are zeros. */
+#define SSDR_GCN_NHID 128
+#define SSDR_GCN_NPARAM 4353
+#define SSDR_GCN_FUSED_CAP 1024
+#define SSDR_GCN_FORM_AUTO 0
+#define SSDR_GCN_FORM_GENERAL 1
+#define SSDR_GCN_FORM_FUSED 2
+#define SSDR_GCN_ST_SINGLETON 32
+#define SSDR_GCN_ST_NO_LABELLED 64
+#define SSDR_GCN_ST_SUBSTITUTED 128
+#define SSDR_GCN_ST_OVERSIZE 256   /* a block above the fused form's cap met on the device (n_max understated): that cloud took no part */
+int ssdr_gcn_block_adj_dev(const float* d_feat, size_t cap_rows, int F, const double* d_centres, const double* d_cd_dir, const int32_t* d_coff, const int64_t* d_boff,
+                           size_t num_clouds, size_t n_max, const int32_t* d_rows, const int32_t* d_counts, float* d_out_v, float* d_out_adj, float* d_out_adjT,
+                           int32_t* d_rowcloud, int32_t* d_info, void* stream);
+int ssdr_gcn_train_dev(const float* d_v, const float* d_adj, const float* d_adjT, const int32_t* d_coff, const int64_t* d_boff, size_t num_clouds, size_t n_max,
+                       const int32_t* d_rows, const int32_t* d_rowcloud, const int32_t* d_counts, size_t cap_rows, const float* d_init, float* d_trained, int steps,
+                       float p, float lr, float weight_decay, float lamda, uint64_t seed, int form, float* d_loss, int32_t* d_info, void* stream);
+int ssdr_gcn_eval_dev(const float* d_v, const float* d_adj, const float* d_adjT, const int32_t* d_coff, const int64_t* d_boff, size_t num_clouds, size_t n_max,
+                      const int32_t* d_rows, const int32_t* d_rowcloud, const int32_t* d_counts, size_t cap_rows, const float* d_params, double* d_out, int32_t* d_info,
+                      void* stream);
+/* sampling()'s "gcn" branch as ONE enqueue-only call: the candidate rule, compute_features, bbox centres and chamfer means of ssdr_gcn_fps_sampling_dev
+ * (same arguments, same d_result layout: counts, picks at word 8, the candidate list followed by the labelled regions), then block adjacency -> training
+ * from d_init -> evaluation -> kCenterGreedy over candidates + labelled rows seeded with the labelled ones (kcenterGreedy.py:84-128) over the 129-d rows.
+ * d_result[5] also carries SSDR_GCN_ST_SINGLETON / SSDR_GCN_ST_NO_LABELLED (the picks mean nothing then); substitutions are no failure and are reported
+ * by the accessor's d_info alone.  coreGCN = False (gcn.py:251-255) has no call site in the reference and is not offered. */
+int ssdr_gcn_sampling_dev(const float* d_feat, int feat_dim, const int32_t* d_cls, const int32_t* d_dom, const int32_t* d_lab_cls, const int32_t* d_lab_dom,
+                          const float* d_xyz, const int32_t* d_sp_off, const int32_t* d_sp_pts, const int32_t* d_order, size_t S, const uint8_t* d_labelled, const int32_t* d_sp_base, size_t num_clouds,
+                          const int32_t* d_lab_off, const int32_t* d_lab_sp, size_t n_lab, size_t batch_size, const float* d_init, int steps, float p, float lr, float weight_decay,
+                          float lamda, uint64_t seed, int form, size_t cap_rows, size_t cap_nmax, size_t cap_sq, size_t cap_unl, size_t max_select, int32_t* d_result, void* stream);
+/* What the last ssdr_gcn_sampling_dev call on `stream` left on the device: the evaluation rows [cap_rows][129] float64 (candidates first, then the
+ * labelled regions), the trained parameters, d_loss [2] and d_info [8] as above (each may be NULL).  Valid until the next such call on that stream. */
+int ssdr_gcn_sampling_rows(void* stream, const double** d_rows, size_t* cap_rows, const float** d_params, const float** d_loss, const int32_t** d_info);
 /* The candidate rule of sampling() + GCN_FPS_sampling as ONE enqueue-only call (S3/sampler2.py:533-552 create_file_top_and_all, :745-753 the
  * "first 2 x selected_num regions of a cloud" rule, :313-342 / :736-781 GCN_FPS_sampling; fps_gcn_cpu.py:60-178): the ranking goes in, the selected
  * candidates come out, and no host decision sits in between — the row counts the rule finds stay on the device and every kernel behind it reads them

@@ -18,6 +18,7 @@
 #include "select_chamfer.hpp"
 #include "select_fps.hpp"
 #include "select_region.hpp"
+#include "select_gcn.hpp"
 
 namespace ssdr {
 namespace {
@@ -1045,6 +1046,50 @@ int ssdr_create_adj_dev(const float* d_feat, size_t N, int F, const double* d_ce
     return SSDR_OK;
 }
 
+}  // extern "C"
+
+// What ssdr_gcn_fps_sampling_dev and ssdr_gcn_sampling_dev share: the candidate rule (four small kernels, cand_*), compute_features of the candidates and
+// the labelled regions, the chamfer packer with the bbox centres, and the directed chamfer means — everything up to the adjacency, which differs.
+struct SamplingFront { int* counts; int* out; int* sel; int* coff; long long* boff; int* gsel; int* rows; int* already;
+                       double* V; double* comb; double* tmp0; double* tmp1; double* cen; double* dir; double* adj; int nm; unsigned nc; };
+// feat32 (optional, [cap_rows, 32]): the float32 rows of compute_features next to their widened copies
+static int sampling_front(SelState& Q, hipStream_t s, const float* d_feat, int D, const int32_t* d_cls, const int32_t* d_dom, const int32_t* d_lab_cls, const int32_t* d_lab_dom,
+                          const float* d_xyz, const int32_t* d_sp_off, const int32_t* d_sp_pts, const int32_t* d_order, size_t S, const uint8_t* d_labelled, const int32_t* d_sp_base,
+                          size_t num_clouds, const int32_t* d_lab_off, const int32_t* d_lab_sp, size_t n_lab, size_t batch_size, size_t cap_rows, size_t cap_nmax, size_t cap_sq,
+                          size_t max_select, int32_t* d_result, float* feat32, std::optional<ProfScope>& prof, SamplingFront& R) {
+    const int B = (int)num_clouds, nchunks = (int)((S + CR_NT - 1) / CR_NT);
+    // ints: rankpos S, cploc S, stage S, chunk nchunks, ncand B, ntop B, uoff B+1, coff B+1, gsel cap, rows cap | int64: boff B+1
+    const size_t ni = 3 * S + (size_t)nchunks + 4 * (size_t)B + 2 + 2 * cap_rows + n_lab + 16;
+    SSDR_TRY(Q.cand_i.reserve(4 * ni + 8 * ((size_t)B + 2)));
+    int* rankpos = Q.cand_i.as<int>(); int* cploc = rankpos + S; int* stage = cploc + S; int* chunk = stage + S; int* ncand = chunk + nchunks; int* ntop = ncand + B;
+    int* uoff = ntop + B; int* coff = uoff + B + 1; int* gsel = coff + B + 1; int* rows = gsel + cap_rows; int* already = rows + cap_rows;
+    long long* boff = reinterpret_cast<long long*>(Q.cand_i.as<char>() + ((4 * ni + 7) & ~(size_t)7));
+    // doubles: V, comb, tmp0, tmp1 [cap_rows, D]; centres [cap_rows, 3]; dir, adj [cap_sq]
+    SSDR_TRY(Q.cand_f.reserve(8 * (4 * cap_rows * D + 3 * cap_rows + 2 * cap_sq)));
+    double* V = Q.cand_f.as<double>(); double* comb = V + cap_rows * D; double* tmp0 = comb + cap_rows * D; double* tmp1 = tmp0 + cap_rows * D;
+    double* cen = tmp1 + cap_rows * D; double* dir = cen + 3 * cap_rows; double* adj = dir + cap_sq;
+    int* counts = d_result; int* out = d_result + 8; int* sel = out + max_select;
+    prof.emplace("sel_candidate_rule", s, 0.0);
+    hipLaunchKernelGGL(cand_rank, dim3(nchunks), dim3(CR_NT), 0, s, d_order, (int)S, d_labelled, rankpos, cploc, chunk);
+    hipLaunchKernelGGL(cand_chunkscan, dim3(1), dim3(256), 0, s, chunk, nchunks);
+    hipLaunchKernelGGL(cand_cloud, dim3(B, cand_slices((size_t)S, (size_t)B)), dim3(256), 0, s, rankpos, cploc, chunk, d_labelled, d_sp_base, (int)S, (int)std::min<size_t>(batch_size, 0x7fffffff), stage, ncand, ntop);
+    hipLaunchKernelGGL(cand_layout, dim3(1), dim3(256), 0, s, ncand, ntop, d_lab_off, B, (long long)cap_rows, (long long)cap_sq, uoff, coff, boff, counts);
+    hipLaunchKernelGGL(cand_fill, dim3(B), dim3(256), 0, s, stage, d_sp_base, ncand, uoff, coff, d_lab_off, d_lab_sp, counts, sel, gsel, rows, already);
+    const int nt = (int)cap_rows, nm = (int)cap_nmax; const unsigned nc = (unsigned)B;
+    prof.emplace("sel_features_pack", s, 0.0);
+    // compute_features (sampler2.py:333,339) of the refs, widened; bbox centres of the grouped rows
+    hipLaunchKernelGGL(sel_segment_mean, dim3(grid_for((long)nt * D)), dim3(256), 0, s, d_feat, D, d_cls, d_dom, d_sp_off, d_sp_pts, sel, nt, feat32, counts + 2, V, comb,
+                       d_lab_cls, d_lab_dom, counts);
+    SSDR_TRY(Q.rowsum.reserve(8 * cap_rows));
+    ChamferPack P; SSDR_TRY(chamfer_pack_buffers(Q, cap_rows, num_clouds, P));
+    SSDR_TRY(chamfer_pack_launch(P, d_xyz, d_sp_off, d_sp_pts, gsel, coff, 0, cap_rows, nm, nc, cen, s));
+    prof.emplace("sel_chamfer", s, 0.0);          // (pairs of points: the counts are the device's; bench.py derives the FLOPs from the result)
+    SSDR_TRY(chamfer_dir_batch_launch(d_xyz, d_sp_off, d_sp_pts, gsel, coff, boff, nm, nc, cen, dir, P, s));
+    R = SamplingFront{counts, out, sel, coff, boff, gsel, rows, already, V, comb, tmp0, tmp1, cen, dir, adj, nm, nc};
+    return SSDR_OK;
+}
+
+extern "C" {
 /* GCN_FPS_sampling (sampler2.py:313-342, :736-781) behind the candidate rule of its caller (sampler2.py:533-552, :745-753), with no host decision in
  * between: ranking in, selected candidates out.  The candidate rule runs as four small kernels (cand_*); the row counts it finds stay on the device and
  * every kernel behind it (features, bbox centres, chamfer packer, chamfer, adjacency, keep-top mask, propagation hops, FPS) reads them there, its launch
@@ -1061,51 +1106,57 @@ int ssdr_gcn_fps_sampling_dev(const float* d_feat, int feat_dim, const int32_t* 
     }
     SSDR_TRY(ensure_init());
     hipStream_t s = pick_stream(stream); SelState& Q = sst(s);
-    const int B = (int)num_clouds, nchunks = (int)((S + CR_NT - 1) / CR_NT), D = feat_dim;
-    // ints: rankpos S, cploc S, stage S, chunk nchunks, ncand B, ntop B, uoff B+1, coff B+1, gsel cap, rows cap | int64: boff B+1
-    const size_t ni = 3 * S + (size_t)nchunks + 4 * (size_t)B + 2 + 2 * cap_rows + n_lab + 16;
-    SSDR_TRY(Q.cand_i.reserve(4 * ni + 8 * ((size_t)B + 2)));
-    int* rankpos = Q.cand_i.as<int>(); int* cploc = rankpos + S; int* stage = cploc + S; int* chunk = stage + S; int* ncand = chunk + nchunks; int* ntop = ncand + B;
-    int* uoff = ntop + B; int* coff = uoff + B + 1; int* gsel = coff + B + 1; int* rows = gsel + cap_rows; int* already = rows + cap_rows;
-    long long* boff = reinterpret_cast<long long*>(Q.cand_i.as<char>() + ((4 * ni + 7) & ~(size_t)7));
-    // doubles: V, comb, tmp0, tmp1 [cap_rows, D]; centres [cap_rows, 3]; dir, adj [cap_sq]
-    SSDR_TRY(Q.cand_f.reserve(8 * (4 * cap_rows * D + 3 * cap_rows + 2 * cap_sq)));
-    double* V = Q.cand_f.as<double>(); double* comb = V + cap_rows * D; double* tmp0 = comb + cap_rows * D; double* tmp1 = tmp0 + cap_rows * D;
-    double* cen = tmp1 + cap_rows * D; double* dir = cen + 3 * cap_rows; double* adj = dir + cap_sq;
-    Q.last_comb = comb; Q.last_cap = cap_rows;
-    int* counts = d_result; int* out = d_result + 8; int* sel = out + max_select;
-    std::optional<ProfScope> prof; prof.emplace("sel_candidate_rule", s, 0.0);
-    hipLaunchKernelGGL(cand_rank, dim3(nchunks), dim3(CR_NT), 0, s, d_order, (int)S, d_labelled, rankpos, cploc, chunk);
-    hipLaunchKernelGGL(cand_chunkscan, dim3(1), dim3(256), 0, s, chunk, nchunks);
-    hipLaunchKernelGGL(cand_cloud, dim3(B, cand_slices((size_t)S, (size_t)B)), dim3(256), 0, s, rankpos, cploc, chunk, d_labelled, d_sp_base, (int)S, (int)std::min<size_t>(batch_size, 0x7fffffff), stage, ncand, ntop);
-    hipLaunchKernelGGL(cand_layout, dim3(1), dim3(256), 0, s, ncand, ntop, d_lab_off, B, (long long)cap_rows, (long long)cap_sq, uoff, coff, boff, counts);
-    hipLaunchKernelGGL(cand_fill, dim3(B), dim3(256), 0, s, stage, d_sp_base, ncand, uoff, coff, d_lab_off, d_lab_sp, counts, sel, gsel, rows, already);
-    const int nt = (int)cap_rows, nm = (int)cap_nmax; const unsigned nc = (unsigned)B;
-    prof.emplace("sel_features_pack", s, 0.0);
-    // compute_features (sampler2.py:333,339) of the refs, widened; bbox centres of the grouped rows
-    hipLaunchKernelGGL(sel_segment_mean, dim3(grid_for((long)nt * D)), dim3(256), 0, s, d_feat, D, d_cls, d_dom, d_sp_off, d_sp_pts, sel, nt, (float*)nullptr, counts + 2, V, comb,
-                       d_lab_cls, d_lab_dom, counts);
-    SSDR_TRY(Q.rowsum.reserve(8 * cap_rows));
-    ChamferPack P; SSDR_TRY(chamfer_pack_buffers(Q, cap_rows, num_clouds, P));
-    SSDR_TRY(chamfer_pack_launch(P, d_xyz, d_sp_off, d_sp_pts, gsel, coff, 0, cap_rows, nm, nc, cen, s));
-    prof.emplace("sel_chamfer", s, 0.0);          // (pairs of points: the counts are the device's; bench.py derives the FLOPs from the result)
-    SSDR_TRY(chamfer_dir_batch_launch(d_xyz, d_sp_off, d_sp_pts, gsel, coff, boff, nm, nc, cen, dir, P, s));
+    const int D = feat_dim;
+    std::optional<ProfScope> prof; SamplingFront R;
+    SSDR_TRY(sampling_front(Q, s, d_feat, D, d_cls, d_dom, d_lab_cls, d_lab_dom, d_xyz, d_sp_off, d_sp_pts, d_order, S, d_labelled, d_sp_base, num_clouds, d_lab_off, d_lab_sp, n_lab,
+                            batch_size, cap_rows, cap_nmax, cap_sq, max_select, d_result, nullptr, prof, R));
+    Q.last_comb = R.comb; Q.last_cap = cap_rows;
+    const int nm = R.nm; const unsigned nc = R.nc;
     prof.emplace("sel_adjacency_propagate", s, 0.0);
-    hipLaunchKernelGGL(sel_adj_build_batch, dim3(std::min(nm, 1024), 1, nc), dim3(256), 0, s, cen, dir, coff, boff, adj, Q.rowsum.as<double>());
-    hipLaunchKernelGGL(sel_adj_norm_batch, dim3(grid_for((long)nm * nm, 256), 1, nc), dim3(256), 0, s, Q.rowsum.as<double>(), coff, boff, adj);
-    if (gcn_top > 0) hipLaunchKernelGGL(sel_adj_topk_batch, dim3(std::max(1, std::min((nm + 3) / 4, 1024)), 1, nc), dim3(256), 0, s, adj, coff, boff, gcn_top);
-    const double* src = V;
+    hipLaunchKernelGGL(sel_adj_build_batch, dim3(std::min(nm, 1024), 1, nc), dim3(256), 0, s, R.cen, R.dir, R.coff, R.boff, R.adj, Q.rowsum.as<double>());
+    hipLaunchKernelGGL(sel_adj_norm_batch, dim3(grid_for((long)nm * nm, 256), 1, nc), dim3(256), 0, s, Q.rowsum.as<double>(), R.coff, R.boff, R.adj);
+    if (gcn_top > 0) hipLaunchKernelGGL(sel_adj_topk_batch, dim3(std::max(1, std::min((nm + 3) / 4, 1024)), 1, nc), dim3(256), 0, s, R.adj, R.coff, R.boff, gcn_top);
+    const double* src = R.V;
     for (int hop = 0; hop < gcn_number; ++hop) {
-        double* dst = (hop & 1) ? tmp1 : tmp0;
-        hipLaunchKernelGGL(sel_propagate_batch, dim3(grid_for((long)nm * D, 256), 1, nc), dim3(256), 0, s, adj, coff, boff, rows, src, D, dst, comb);
+        double* dst = (hop & 1) ? R.tmp1 : R.tmp0;
+        hipLaunchKernelGGL(sel_propagate_batch, dim3(grid_for((long)nm * D, 256), 1, nc), dim3(256), 0, s, R.adj, R.coff, R.boff, R.rows, src, D, dst, R.comb);
         src = dst;
     }
     SSDR_HIP(hipGetLastError());
     prof.reset();
     if (max_select == 0) return SSDR_OK;
     // selector 1: kCenterGreedy over candidates + labelled rows, seeded with the labelled ones (kcenterGreedy.py:84-128; sampler2.py's "kcenter" branch)
-    if (selector == 1) return fps_like(comb, cap_rows, D, already, n_lab, 0, max_select, 1, out, s, counts + 2);
-    return fps_like(comb, cap_unl, D, nullptr, 0, start, max_select, 0, out, s, counts);
+    if (selector == 1) return fps_like(R.comb, cap_rows, D, R.already, n_lab, 0, max_select, 1, R.out, s, R.counts + 2);
+    return fps_like(R.comb, cap_unl, D, nullptr, 0, start, max_select, 0, R.out, s, R.counts);
+}
+
+/* sampling()'s "gcn" branch (sampler2.py:687-734 -> gcn.py:193-263) behind the same candidate rule, features, bbox centres and chamfer means: block
+ * adjacency -> Adam training of the two-layer GCN -> evaluation -> kCenterGreedy over the 129-d rows, seeded with the labelled ones (select_gcn.hip). */
+int ssdr_gcn_sampling_dev(const float* d_feat, int feat_dim, const int32_t* d_cls, const int32_t* d_dom, const int32_t* d_lab_cls, const int32_t* d_lab_dom,
+                          const float* d_xyz, const int32_t* d_sp_off, const int32_t* d_sp_pts, const int32_t* d_order, size_t S, const uint8_t* d_labelled, const int32_t* d_sp_base, size_t num_clouds,
+                          const int32_t* d_lab_off, const int32_t* d_lab_sp, size_t n_lab, size_t batch_size, const float* d_init, int steps, float p, float lr, float weight_decay,
+                          float lamda, uint64_t seed, int form, size_t cap_rows, size_t cap_nmax, size_t cap_sq, size_t cap_unl, size_t max_select, int32_t* d_result, void* stream) {
+    if (!d_feat || !d_cls || !d_dom || (!d_lab_cls != !d_lab_dom) || !d_xyz || !d_sp_off || !d_sp_pts || !d_order || !d_labelled || !d_sp_base || !d_lab_off || !d_result || !d_init || feat_dim != 32 ||
+        num_clouds == 0 || num_clouds > 65535 || S == 0 || S > 0x7ffffff0 || cap_rows == 0 || cap_nmax == 0 || cap_sq == 0 || cap_unl == 0 || cap_rows > (1u << 22) || steps < 0 || (n_lab && !d_lab_sp)) {
+        set_error("gcn_sampling: bad arguments (feat_dim == 32, at most 2^22 candidate + labelled rows, at most 65535 clouds)"); return SSDR_ERR_INVALID;
+    }
+    if (form == SSDR_GCN_FORM_FUSED && cap_nmax > (size_t)SSDR_GCN_FUSED_CAP) { set_error("gcn_sampling: the fused form holds blocks of at most %d rows (cap_nmax = %zu)", SSDR_GCN_FUSED_CAP, cap_nmax); return SSDR_ERR_INVALID; }
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream); SelState& Q = sst(s);
+    GcnChainBufs G; SSDR_TRY(gcn_chain_buffers(s, cap_rows, cap_sq, G));
+    std::optional<ProfScope> prof; SamplingFront R;
+    SSDR_TRY(sampling_front(Q, s, d_feat, feat_dim, d_cls, d_dom, d_lab_cls, d_lab_dom, d_xyz, d_sp_off, d_sp_pts, d_order, S, d_labelled, d_sp_base, num_clouds, d_lab_off, d_lab_sp, n_lab,
+                            batch_size, cap_rows, cap_nmax, cap_sq, max_select, d_result, G.feat, prof, R));
+    prof.emplace("sel_gcn_train", s, 0.0);
+    int* rowcloud = G.info + 8;
+    SSDR_TRY(ssdr_gcn_block_adj_dev(G.feat, cap_rows, 32, R.cen, R.dir, R.coff, (const int64_t*)R.boff, num_clouds, cap_nmax, R.rows, R.counts, G.v, G.adj, G.adjT, rowcloud, G.info, s));
+    SSDR_TRY(ssdr_gcn_train_dev(G.v, G.adj, G.adjT, R.coff, (const int64_t*)R.boff, num_clouds, cap_nmax, R.rows, rowcloud, R.counts, cap_rows, d_init, G.params, steps, p, lr, weight_decay,
+                                lamda, seed, form, G.loss, G.info, s));
+    SSDR_TRY(ssdr_gcn_eval_dev(G.v, G.adj, G.adjT, R.coff, (const int64_t*)R.boff, num_clouds, cap_nmax, R.rows, rowcloud, R.counts, cap_rows, G.params, G.rows129, G.info, s));
+    SSDR_TRY(gcn_merge_status(G.info, R.counts, s));
+    prof.reset();
+    if (max_select == 0 || n_lab == 0) return SSDR_OK;
+    return fps_like(G.rows129, cap_rows, 129, R.already, n_lab, 0, max_select, 1, R.out, s, R.counts + 2);
 }
 
 /* The propagated rows of the last ssdr_gcn_fps_sampling_dev call on `stream` (device pointer, [cap_rows][32] float64: the candidates first, then the labelled

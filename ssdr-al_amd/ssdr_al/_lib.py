@@ -112,6 +112,12 @@ def lib():
         L.ssdr_event_create.argtypes = [C.POINTER(vp)]; L.ssdr_event_record.argtypes = [vp, vp]; L.ssdr_stream_wait_event.argtypes = [vp, vp]; L.ssdr_event_destroy.argtypes = [vp]
         L.ssdr_select_set_chamfer_mode.argtypes = [i32]
         L.ssdr_gcn_fps_sampling_rows.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
+        u64 = C.c_uint64
+        L.ssdr_gcn_block_adj_dev.argtypes = [vp, sz, i32, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.ssdr_gcn_train_dev.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, i32, f32, f32, f32, f32, u64, i32, vp, vp, vp]
+        L.ssdr_gcn_eval_dev.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
+        L.ssdr_gcn_sampling_dev.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, sz, vp, i32, f32, f32, f32, f32, u64, i32, sz, sz, sz, sz, sz, vp, vp]
+        L.ssdr_gcn_sampling_rows.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.ssdr_kcenter_gathered_dev.argtypes = [vp, vp, i32, sz, sz, vp, sz, sz, sz, vp, vp, vp, vp]
         L.ssdr_fps_gathered_dev.argtypes = [vp, vp, i32, sz, sz, i32, i32, sz, vp, vp, vp]
         L.ssdr_kcenter_dev.argtypes = [vp, sz, i32, vp, sz, sz, vp, vp]

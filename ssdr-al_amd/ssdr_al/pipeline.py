@@ -47,18 +47,22 @@ class _Pairs:
         return repr(self.tolist())
 
 
-SELECTORS = ("fps", "kcenter", "edcd", "topk")
+SELECTORS = ("fps", "kcenter", "edcd", "topk", "coregcn")
 
 
-def selector_for(sampler_args):
+def selector_for(sampler_args, trained_gcn=False):
     """The selector that runs the branch of TSampler.sampling() a reference `sampler_args` names, tested in the reference's elif order
-    (sampler2.py:670, :687, :736, :783): "edcd", "gcn" (not offered), "gcn_fps", else uncertainty alone."""
+    (sampler2.py:670, :687, :736, :783): "edcd", "gcn", "gcn_fps", else uncertainty alone.  The "gcn" branch trains a GCN during selection (minutes in
+    the reference): it is named only on request — trained_gcn=True returns "coregcn" for it, the default keeps refusing it."""
     args = list(sampler_args)
     if "edcd" in args:
         return "edcd"
+    if "gcn" in args and trained_gcn:
+        return "coregcn"
     if "gcn" in args:
         raise ValueError('sampler_args names the "gcn" branch (a GCN trained during selection, sampler2.py:687-734), which is out of scope here; '
-                         'selector="kcenter" runs its last step (kCenterGreedy over candidates + labelled regions)')
+                         'selector="kcenter" runs its last step (kCenterGreedy over candidates + labelled regions), and selector_for(args, trained_gcn=True) '
+                         'names the selector that trains the GCN ("coregcn")')
     if "gcn_fps" in args:
         return "fps"
     return "topk"
@@ -67,7 +71,7 @@ def selector_for(sampler_args):
 class HotPath:
     def __init__(self, weights, config=ConfigS3DIS, sampler_args=("sb", "WetSU", "clsbal", "gcn_fps"), gcn_number=1, gcn_top=0,
                  select_per_tile=37, labeled_per_tile=15, seed=0, precision="f32", selector="fps", tiles32=True, min_size=1, round_num=5,
-                 label_seed=None, batch_size=None, max_size=None, chamfer_mode="f64"):
+                 label_seed=None, batch_size=None, max_size=None, chamfer_mode="f64", gcn_steps=20000, gcn_dropout=0.3, gcn_seed=0, gcn_form="auto"):
         self.cfg = config
         self.net = None if weights is None else randlanet.Network(config).load(weights).set_precision(precision).set_formulation(tiles32)
         self.sampler_args = list(sampler_args)
@@ -89,8 +93,11 @@ class HotPath:
         # (the step the reference's gcn branch ends with, gcn.py:247, kcenterGreedy.py:60-128; BASELINE configuration 4's global k-center);
         # "edcd": every cloud's farthest_superpoint_sample over its candidates (sampler2.py:670-685, :49-80), always with the float64 chamfer;
         # "topk": the first batch_size regions of the ranking (sampler2.py:783-806).  selector_for() maps a reference sampler_args to one of them
+        # "coregcn": the reference's "gcn" branch (sampler2.py:687-734 -> gcn.py:193-263): create_adj, gcn_steps Adam steps of the two-layer GCN (20 000 on
+        # S3DIS, 2 000 on Semantic3D) from the weights gcn_seed draws, dropout gcn_dropout, then kCenterGreedy over the trained 129-d rows
         assert selector in SELECTORS, "selector must be one of %s" % (SELECTORS,)
         self.selector = selector
+        self.gcn_steps, self.gcn_dropout, self.gcn_seed, self.gcn_form = int(gcn_steps), float(gcn_dropout), int(gcn_seed), gcn_form
         self.fps_start = 0          # np.random.randint(0, n) in the reference (fps_gcn_cpu.py:133); fixed here
         self.stream = None          # stream of the pyramid .. scoring stages (None = the library's main stream)
         self.front_stream = None    # stream of the front end (grid-subsample + tiles)
@@ -222,6 +229,8 @@ class HotPath:
 
     def step_selection(self, comm=None):
         """scoring + selection over the resident network outputs (from_clouds); comm: the sharded run's exchanges"""
+        if comm is not None and self.selector == "coregcn":
+            raise ValueError('selector="coregcn" with a communicator: the sharded form of the trained-GCN selector is not offered')
         self._score_async(comm)
         return self._select(comm)
 
@@ -502,6 +511,21 @@ class HotPath:
         _lib.check(L.ssdr_select_set_chamfer_mode(self.chamfer_mode))
         T = self._sel_static
         kc = self.selector == "kcenter"
+        if self.selector == "coregcn":
+            from . import sampler
+            if comm is not None or self.global_order is not None:
+                raise ValueError('selector="coregcn" with a communicator: the sharded form of the trained-GCN selector is not offered')
+            if T["n_lab"] == 0:
+                raise ValueError("GCN_sampling: no labelled row: the loss is a mean over an empty set (gcn.py:81-83)")
+            self._gcn_init = DevArray.from_host(sampler.gcn_init_params(self.gcn_seed), st)
+            _lib.check(L.ssdr_gcn_sampling_dev(self.f32.ptr, 32, self.cls.ptr, self.dom.ptr, self.tile_l.ptr, self.gt_dom.ptr, self.xyz.ptr, self.sp_off.ptr, self.sp_pts.ptr,
+                                               self.sorted_inds.ptr, self.S, T["d_lab"].ptr, T["d_base"].ptr, self.B, T["d_lab_off"].ptr, T["d_lab_sp"].ptr,
+                                               T["n_lab"], T["batch"], self._gcn_init.ptr, self.gcn_steps, self.gcn_dropout, 1e-3, 5e-4, 1.2,
+                                               self.gcn_seed & 0xffffffffffffffff, sampler.GCN_FORMS[self.gcn_form], T["cap_rows"], T["cap_nmax"], T["cap_sq"],
+                                               T["cap_unl"], T["picks"], T["d_result"].ptr, st))
+            self._pending = ("device", None)
+            self.rule_path = "device"
+            return
         if (self.global_order is None and T["picks"] > 0 and (not kc or T["n_lab"] > 0)
                 and not os.environ.get("SSDR_SELECT_HOST_RULE")):
             # candidate rule + GCN_FPS_sampling enqueued as one chain: the host decides nothing and uploads nothing (the result is read in _select_collect)
@@ -758,6 +782,10 @@ class HotPath:
             res = d_res.to_host(self.sel_stream)             # waits for the selection stream alone
             # from ~20 tiles per GPU on the chain's FPS / k-center is a cooperative launch: one that was not co-resident reports it here
             _lib.check(_lib.lib().ssdr_select_status(self.sel_stream, None))
+            if self.selector == "coregcn":
+                from . import sampler
+                self.gcn_info = info = self.gcn_rows(info_only=True)
+                sampler.gcn_status_check(info, self.room_ids)
             if res[5] & ~3:
                 raise RuntimeError("edcd_sampling: %s (status %d): nothing was selected" % (
                     "a cloud has more than 8192 candidates" if res[5] & 4 else "the picks do not fit the capacities", int(res[5])))
@@ -798,6 +826,21 @@ class HotPath:
         self._last_sel = where      # where the picks of this selection lie, for label_selected (None: a sharded round)
         self._selected = _Pairs(np.asarray(self.unl_cloud_ids)[si], np.asarray(self.unl_sp)[si])      # (room id, superpoint in room)
         return sel, unl
+
+    def gcn_rows(self, info_only=False):
+        """what the last "coregcn" selection left on the device: (evaluation rows [rows,129] float64, trained parameters, (loss at step 0, loss after the
+        last step), info) — info = [status bits, first single-row cloud, substituted values, form]"""
+        L, st = _lib.lib(), self.sel_stream
+        p_rows, cap, p_par, p_loss, p_info = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _lib.check(L.ssdr_gcn_sampling_rows(st, C.byref(p_rows), C.byref(cap), C.byref(p_par), C.byref(p_loss), C.byref(p_info)))
+        info = np.empty(8, np.int32)
+        _lib.check(L.ssdr_memcpy_d2h_on(_lib.ptr(info), p_info.value, info.nbytes, st))
+        if info_only:
+            return info
+        rows = np.empty((int(cap.value), 129), np.float64); par = np.empty(4353, np.float32); loss = np.empty(2, np.float32)
+        _lib.check(L.ssdr_memcpy_d2h_on(_lib.ptr(rows), p_rows.value, rows.nbytes, st)); _lib.check(L.ssdr_memcpy_d2h_on(_lib.ptr(par), p_par.value, par.nbytes, st))
+        _lib.check(L.ssdr_memcpy_d2h_on(_lib.ptr(loss), p_loss.value, loss.nbytes, st))
+        return rows, par, loss, info
 
     @property
     def selected(self):
@@ -944,7 +987,7 @@ class ALRound:
     SLOTS = 4          # batches in flight = HIP streams = the runtime's hardware queues (2: 54.9 ms for 17 batches, 3: 52.2, 4: 49.1, 5: 56.9, 6: 49.4, 8: 49.6; a stream per STAGE: 60-64)
 
     def __init__(self, weights, rooms, n_batches, config=ConfigS3DIS, batch_size=10000, round_num=5, labeled_per_tile=15, precision="f32",
-                 selector="fps", tiles32=True, seed=0, gcn_number=1, gcn_top=0, min_size=1):
+                 selector="fps", tiles32=True, seed=0, gcn_number=1, gcn_top=0, min_size=1, gcn_steps=20000, gcn_dropout=0.3, gcn_seed=0, gcn_form="auto"):
         L = _lib.lib()
         self.cfg, self.nb, self.B, self.rooms = config, int(n_batches), len(rooms), rooms
         N = config.num_points
@@ -1003,7 +1046,8 @@ class ALRound:
             labeled[t] = set((base + rng.choice(n_sp, min(labeled_per_tile, n_sp), replace=False)).tolist())
         sel_list = np.random.default_rng([seed, 999983]).integers(0, config.num_classes, 4000)
         self.sel = HotPath.from_device(self.xyz, self.probs, self.f32, self.tile_l, np.concatenate(offs), np.concatenate(pts), np.concatenate(cloud), labeled, sel_list,
-                                       config, batch_size=batch_size, round_num=round_num, selector=selector, gcn_number=gcn_number, gcn_top=gcn_top, min_size=min_size, seed=seed)
+                                       config, batch_size=batch_size, round_num=round_num, selector=selector, gcn_number=gcn_number, gcn_top=gcn_top, min_size=min_size, seed=seed,
+                                       gcn_steps=gcn_steps, gcn_dropout=gcn_dropout, gcn_seed=gcn_seed, gcn_form=gcn_form)
         self.sel.stream = self.sel.score_stream = self.sel.sel_stream = s_i
         self.sel.front_stream = s_i; self.sel.pipelined = True
         self.sel.pt_off = np.arange(self.tiles + 1, dtype=np.int64) * N

@@ -336,3 +336,157 @@ def GCN_FPS_sampling(labeled_select_features, labeled_select_ref, unlabeled_cand
         r = unlabeled_candidate_ref[int(i)]
         file_list.setdefault(r["cloud_name"], []).append(r["sp_idx"])
     return file_list
+
+
+# ---- the trained-GCN selector: gcn.GCN_sampling (gcn.py:193-263), csrc/select_gcn.hip -------------------------------------------------------
+GCN_NPARAM, GCN_FUSED_CAP = 4353, 1024
+GCN_FORMS = {"auto": 0, "general": 1, "fused": 2}
+GCN_ST_SINGLETON, GCN_ST_NO_LABELLED, GCN_ST_SUBSTITUTED, GCN_ST_OVERSIZE = 32, 64, 128, 256
+
+
+def gcn_init_params(seed):
+    """The initial W1 [32,128], b1 [128], W3 [128], b3 [1] as one float32 array, drawn as GraphConvolution.reset_parameters does (gcn.py:32-36):
+    uniform +-1/sqrt(out_features), i.e. +-1/sqrt(128) for gc1 and +-1 for gc3 — from NumPy's generator seeded with `seed` (the reference draws from
+    torch's global one)."""
+    rng = np.random.RandomState(int(seed) & 0xffffffff)
+    s = 1.0 / np.sqrt(128.0)
+    return np.concatenate([rng.uniform(-s, s, 32 * 128), rng.uniform(-s, s, 128), rng.uniform(-1.0, 1.0, 128), rng.uniform(-1.0, 1.0, 1)]).astype(np.float32)
+
+
+def gcn_status_check(info, cloud_names=None):
+    """ValueError for what the reference would train on NaN for: a cloud with a single row (zero column sum), no labelled row (empty mean)."""
+    st = int(info[0])
+    if st & GCN_ST_SINGLETON:
+        c = int(info[1])
+        name = cloud_names[c] if cloud_names is not None and 0 <= c < len(cloud_names) else c
+        raise ValueError("GCN_sampling: cloud %r contributes a single row to the graph: its adjacency column sums to 0 (the reference divides by it, "
+                         "gcn.py:185-187)" % (name,))
+    if st & GCN_ST_NO_LABELLED:
+        raise ValueError("GCN_sampling: no labelled row: the loss is a mean over an empty set (gcn.py:81-83)")
+    if st & GCN_ST_OVERSIZE:
+        raise ValueError("GCN_sampling: a cloud's block exceeds the fused form's %d rows (n_max understated)" % GCN_FUSED_CAP)
+
+
+class GcnGraph:
+    """The block adjacency of the trained-GCN branch on the device, and the calls that run over it.  rows[g] = the row (in the reference's
+    [unlabelled | labelled] order) of grouped position g; counts = rows per cloud.  cap_rows > the live row count leaves spare (never read) rows."""
+
+    def __init__(self, counts, rows, n_unl, cap_rows=None, cloud_names=None):
+        counts = np.asarray(counts, np.int64)
+        self.counts, self.rows_h = counts, np.asarray(rows, np.int32)
+        self.N = int(counts.sum()); self.n_unl = int(n_unl); self.n_lab = self.N - self.n_unl
+        self.cap = int(cap_rows or self.N); self.B = len(counts); self.n_max = int(counts.max())
+        self.cloud_names = cloud_names
+        self.coff = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32); self.boff = np.concatenate([[0], np.cumsum(counts * counts)]).astype(np.int64)
+        self.d_coff, self.d_boff = DevArray.from_host(self.coff), DevArray.from_host(self.boff)
+        self.d_rows = DevArray.from_host(np.concatenate([self.rows_h, np.zeros(self.cap - self.N, np.int32)]))
+        self.d_counts = DevArray.from_host(np.array([self.n_unl, self.n_lab, self.N, self.n_max, 0, 0, 0, 0], np.int32))
+        self.d_v = DevArray((self.cap, 32), np.float32); self.d_adj = DevArray((int(self.boff[-1]),), np.float32); self.d_adjT = DevArray((int(self.boff[-1]),), np.float32)
+        self.d_rowcloud = DevArray((self.cap,), np.int32); self.d_info = DevArray((8,), np.int32)
+
+    @classmethod
+    def from_clouds(cls, featuresV, labeled_select_ref, unlabeled_candidate_ref, clouds, cap_rows=None):
+        """create_adj's inputs (see create_adj above) -> the blocks, by ssdr_cloud_graph_batch_dev + ssdr_gcn_block_adj_dev"""
+        f = np.ascontiguousarray(featuresV, np.float32)
+        N = len(f)
+        total_cloud, order = {}, []
+        for i, r in enumerate(list(unlabeled_candidate_ref) + list(labeled_select_ref)):
+            if r["cloud_name"] not in total_cloud:
+                total_cloud[r["cloud_name"]] = []
+                order.append(r["cloud_name"])
+            total_cloud[r["cloud_name"]].append((r["sp_idx"], i))
+        xyzs, offs, ptss, sel, rows, counts = [], [np.zeros(1, np.int32)], [], [], [], []
+        pbase = sbase = 0
+        for name in order:
+            xyz, off, pts = clouds[name]
+            off = np.ascontiguousarray(off, np.int32)
+            xyzs.append(np.ascontiguousarray(xyz, np.float32)); ptss.append(np.ascontiguousarray(pts, np.int32) + pbase); offs.append(off[1:] + offs[-1][-1])
+            sel += [s + sbase for s, _ in total_cloud[name]]; rows += [i for _, i in total_cloud[name]]; counts.append(len(total_cloud[name]))
+            pbase += len(xyz); sbase += len(off) - 1
+        G = cls(counts, rows, len(unlabeled_candidate_ref), cap_rows, order)
+        L = _lib.lib()
+        d_x = DevArray.from_host(np.concatenate(xyzs)); d_o = DevArray.from_host(np.concatenate(offs).astype(np.int32)); d_p = DevArray.from_host(np.concatenate(ptss))
+        d_s = DevArray.from_host(np.asarray(sel, np.int32))
+        nsq = int(G.boff[-1])
+        d_c = DevArray((N, 3), np.float64); d_dir = DevArray((nsq,), np.float64); d_a = DevArray((nsq,), np.float64)
+        _lib.check(L.ssdr_cloud_graph_batch_dev(d_x.ptr, d_o.ptr, d_p.ptr, d_s.ptr, G.d_coff.ptr, G.d_boff.ptr, G.B, N, G.n_max, 0, d_c.ptr, d_dir.ptr, d_a.ptr, None))
+        pad = np.full((G.cap - N, 32), np.nan, np.float32)
+        d_f = DevArray.from_host(np.concatenate([f, pad]))
+        _lib.check(L.ssdr_gcn_block_adj_dev(d_f.ptr, G.cap, 32, d_c.ptr, d_dir.ptr, G.d_coff.ptr, G.d_boff.ptr, G.B, G.n_max, G.d_rows.ptr, G.d_counts.ptr,
+                                            G.d_v.ptr, G.d_adj.ptr, G.d_adjT.ptr, G.d_rowcloud.ptr, G.d_info.ptr, None))
+        _lib.sync()
+        return G
+
+    @classmethod
+    def from_blocks(cls, V, blocks, rows, n_unl, cap_rows=None):
+        """a graph given outright: V [N,32] (rows in the [unlabelled | labelled] order, taken as they are) and every cloud's adjacency block"""
+        G = cls([len(b) for b in blocks], rows, n_unl, cap_rows)
+        V = np.ascontiguousarray(V, np.float32)
+        _lib.check(_lib.lib().ssdr_memcpy_h2d(G.d_v.ptr, _lib.ptr(np.concatenate([V, np.full((G.cap - G.N, 32), np.nan, np.float32)])), G.cap * 32 * 4))
+        a = np.concatenate([np.ascontiguousarray(b, np.float32).reshape(-1) for b in blocks]); t = np.concatenate([np.ascontiguousarray(np.asarray(b, np.float32).T).reshape(-1) for b in blocks])
+        _lib.check(_lib.lib().ssdr_memcpy_h2d(G.d_adj.ptr, _lib.ptr(a), a.nbytes)); _lib.check(_lib.lib().ssdr_memcpy_h2d(G.d_adjT.ptr, _lib.ptr(t), t.nbytes))
+        rc = np.concatenate([np.repeat(np.arange(G.B, dtype=np.int32), G.counts), np.zeros(G.cap - G.N, np.int32)])
+        _lib.check(_lib.lib().ssdr_memcpy_h2d(G.d_rowcloud.ptr, _lib.ptr(rc), rc.nbytes))
+        info = np.array([0, 0x7fffffff, 0, 0, 0, 0, 0, 0], np.int32)
+        if (G.counts == 1).any():
+            info[0], info[1] = GCN_ST_SINGLETON, int(np.flatnonzero(G.counts == 1)[0])
+        _lib.check(_lib.lib().ssdr_memcpy_h2d(G.d_info.ptr, _lib.ptr(info), info.nbytes))
+        return G
+
+    def info(self):
+        _lib.sync()
+        return self.d_info.to_host()
+
+    def normalised(self):
+        return self.d_v.to_host()[: self.N]
+
+    def blocks(self, transposed=False):
+        a = (self.d_adjT if transposed else self.d_adj).to_host()
+        return [a[self.boff[c]: self.boff[c + 1]].reshape(int(self.counts[c]), int(self.counts[c])) for c in range(self.B)]
+
+    def _graph_args(self):
+        return (self.d_v.ptr, self.d_adj.ptr, self.d_adjT.ptr, self.d_coff.ptr, self.d_boff.ptr, self.B, self.n_max, self.d_rows.ptr, self.d_rowcloud.ptr,
+                self.d_counts.ptr, self.cap)
+
+    def train(self, init, steps, p=0.3, lr=1e-3, weight_decay=5e-4, lamda=1.2, seed=0, form="auto", check=True):
+        """-> (trained parameters [4353] float32, (loss at step 0, loss after the last step), info)"""
+        d_p = DevArray.from_host(np.ascontiguousarray(init, np.float32).reshape(GCN_NPARAM)); d_loss = DevArray((2,), np.float32)
+        _lib.check(_lib.lib().ssdr_gcn_train_dev(*self._graph_args(), d_p.ptr, d_p.ptr, int(steps), float(p), float(lr), float(weight_decay), float(lamda),
+                                                 int(seed) & 0xffffffffffffffff, GCN_FORMS[form], d_loss.ptr, self.d_info.ptr, None))
+        info = self.info()
+        if check:
+            gcn_status_check(info, self.cloud_names)
+        return d_p.to_host(), d_loss.to_host(), info
+
+    def evaluate(self, params, check=True):
+        """-> (rows [N,129] float64 in the [unlabelled | labelled] order, info)"""
+        d_p = DevArray.from_host(np.ascontiguousarray(params, np.float32).reshape(GCN_NPARAM))
+        d_out = DevArray.from_host(np.full((self.cap, 129), -7.0))
+        _lib.check(_lib.lib().ssdr_gcn_eval_dev(*self._graph_args(), d_p.ptr, d_out.ptr, self.d_info.ptr, None))
+        info = self.info()
+        if check:
+            gcn_status_check(info, self.cloud_names)
+        return d_out.to_host(), info
+
+
+def GCN_sampling(labeled_select_features, labeled_select_ref, unlabeled_candidate_features, unlabeled_candidate_ref, clouds, sampling_batch, gcn_gpu=None,
+                 coreGCN=True, steps=20000, dropout=0.3, seed=0, form="auto"):
+    """gcn.GCN_sampling (gcn.py:193-263) with the two on-disk paths replaced by `clouds` {cloud_name: (xyz [n,3] f32, offsets, points)}: create_adj as
+    blocks, `steps` Adam steps of the two-layer GCN from gcn_init_params(seed), the evaluation rows, kCenterGreedy seeded with the labelled rows.
+    gcn_gpu is accepted and ignored.  Returns {cloud_name: [sp_idx, ...]} in selection order."""
+    if not coreGCN:
+        raise NotImplementedError("GCN_sampling: coreGCN=False (uncertainGCN, gcn.py:251-255) has no call site in the reference and is not offered")
+    n_unl, n_lab = len(unlabeled_candidate_ref), len(labeled_select_ref)
+    fu = np.asarray(unlabeled_candidate_features, np.float32).reshape(n_unl, 32); fl = np.asarray(labeled_select_features, np.float32).reshape(n_lab, 32)
+    if n_lab == 0:
+        raise ValueError("GCN_sampling: no labelled row: the loss is a mean over an empty set (gcn.py:81-83)")
+    G = GcnGraph.from_clouds(np.concatenate([fu, fl]), labeled_select_ref, unlabeled_candidate_ref, clouds)
+    gcn_status_check(G.info(), G.cloud_names)
+    params, _, _ = G.train(gcn_init_params(seed), steps, p=dropout, seed=seed, form=form)
+    feat, _ = G.evaluate(params)
+    picks = kCenterGreedy(feat[: G.N]).select_batch_(np.arange(n_unl, n_unl + n_lab), int(sampling_batch))
+    file_list = {}
+    for i in picks:
+        r = unlabeled_candidate_ref[int(i)]
+        file_list.setdefault(r["cloud_name"], []).append(r["sp_idx"])
+    return file_list
