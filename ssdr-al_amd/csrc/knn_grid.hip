@@ -242,22 +242,27 @@ __device__ __forceinline__ void grid_finish(const GridSearchArgs& a, const GridJ
 // The (2R+1)^3 block around a query by MARKING: a lane whose candidate passes `dist < worst` makes its whole wave execute the
 // ~70-instruction sorted insertion, and with 64 queries of the same cells in a wave that is nearly every candidate.  So the scan of
 // the (2R+1)^2 rows of cells only marks the candidates inside the radius the block guarantees (distance from the query to the
-// nearest block face that has cells beyond it) in one 64-bit mask per row — registers only, four loads in flight — and the
+// nearest block face that has cells beyond it) in one 64-bit mask per row — four loads in flight — and the
 // sorted insertion then runs over the marked candidates alone.  With n1 > 0 the two nearest marked candidates with index < n1 are
 // tracked as well (interp_idx of a pyramid = nearest of the prefix, tf_map's sub-sampling).
 // Returns 0: rs holds the final K + 1 best; 1: fewer than K + 1 candidates inside the radius (a larger block is needed);
 // 2: the masks cannot hold this block (a row of more than 64 candidates) or the radius is not positive (query outside the support box).
-// where the records of the cell-sorted array come from: global memory, or the workgroup's LDS copy of the rows of cells its queries touch
-struct SrcGlobal { const float4* S; __device__ __forceinline__ float4 operator()(int, int, int i) const { return S[i]; } };
+// where the records of the cell-sorted array come from: global memory (the lane's parked rows of marks ride along), or the workgroup's LDS copy of
+// the rows of cells its queries touch
+struct SrcGlobal { const float4* S; unsigned* mk; __device__ __forceinline__ float4 operator()(int, int, int i) const { return S[i]; } };
 struct SrcLds {
     const float4* S; const float4* lds; const int* delta; int z0, y0, nys; bool staged;
     __device__ __forceinline__ float4 operator()(int z, int y, int i) const { return staged ? lds[i + delta[(z - z0) * nys + (y - y0)]] : S[i]; }
 };
-template <int K, int R, class Src>
-__device__ __forceinline__ int grid_mark_select(const GridDesc& d, const int* __restrict__ cell, const Src S, float qx, float qy, float qz,
-                                                RegSet<K + 1>& rs, int n1, float& b0, float& b1, int& i0, float& tau) {
+// first half, shared by the two selections below: the guaranteed radius (tau = its square) and the marking scan.  sink(r, mask, first record) is
+// called for every row of cells inside the grid that the masks can hold (r: a compile-time index once unrolled); cnt = the marks of all rows.
+// Returns 0, or 2 as above.
+template <int R, class Src, class Sink>
+__device__ __forceinline__ int grid_mark_rows(const GridDesc& d, const int* __restrict__ cell, const Src S, float qx, float qy, float qz,
+                                              int& cy, int& cz, float& tau, int& cnt, Sink sink) {
     constexpr int W = 2 * R + 1;
-    const int cx = cell_of(qx, d.lo[0], d.inv_c, d.nx), cy = cell_of(qy, d.lo[1], d.inv_c, d.ny), cz = cell_of(qz, d.lo[2], d.inv_c, d.nz);
+    const int cx = cell_of(qx, d.lo[0], d.inv_c, d.nx);
+    cy = cell_of(qy, d.lo[1], d.inv_c, d.ny); cz = cell_of(qz, d.lo[2], d.inv_c, d.nz);
     const int x0 = max(cx - R, 0), x1 = min(cx + R, d.nx - 1);
     // every point outside the block is at least g away (faces on the grid boundary have nothing beyond them)
     float g = FLT_MAX;
@@ -270,17 +275,15 @@ __device__ __forceinline__ int grid_mark_select(const GridDesc& d, const int* __
     if (!(g > 0.f)) return 2;
     tau = FLT_MAX;
     if (g < FLT_MAX) { const float gs = g * 0.99998f - d.slack; if (!(gs > 0.f)) return 2; tau = gs * gs; }      // cell boundaries are rounded fp32 products: stay inside, relatively and absolutely
-    unsigned long long m[W * W]; int rs0[W * W];
-    int cnt = 0; bool long_row = false;
+    cnt = 0; bool long_row = false;
 #pragma unroll
     for (int r = 0; r < W * W; ++r) {
         const int z = cz + r / W - R, y = cy + r % W - R;
-        m[r] = 0ull; rs0[r] = 0;
         if (z < 0 || z >= d.nz || y < 0 || y >= d.ny) continue;
         const int row = (z * d.ny + y) * d.nx;      // x is the fastest cell dimension: the cells x0..x1 of a row are one contiguous range
         const int s = cell[row + x0], e = cell[row + x1 + 1];
-        rs0[r] = s;
         if (e - s > 64) { long_row = true; continue; }
+        unsigned long long m = 0ull;
         for (int i = s; i < e; i += 4) {
             float4 p[4];
 #pragma unroll
@@ -289,29 +292,94 @@ __device__ __forceinline__ int grid_mark_select(const GridDesc& d, const int* __
             for (int u = 0; u < 4; ++u) {
                 const float dx = qx - p[u].x, dy = qy - p[u].y, dz = qz - p[u].z;
                 float dist = dx * dx; dist = dist + dy * dy; dist = dist + dz * dz;
-                if (i + u < e && dist < tau) { m[r] |= 1ull << (i + u - s); ++cnt; }
+                if (i + u < e && dist < tau) { m |= 1ull << (i + u - s); ++cnt; }
             }
         }
+        sink(r, m, s);
     }
-    if (long_row) return 2;
-    if (cnt < K + 1) {
-        if (n1 > 0) {      // the prefix job may still be answerable from the few candidates inside the radius
+    return long_row ? 2 : 0;
+}
+
+// The selection of the default form takes a lane's marks as ONE sequence (row-major, ascending bit: the order decides which of two equal distances
+// enters first), so a wave runs the largest per-lane total of iterations, not the sum over the rows of the largest per-row count.  The row a lane
+// stands in is then a run-time index, which registers cannot take: each lane parks its non-empty rows (mask, first record) in LDS words
+// [3 * row + k][thread] — bank = thread whatever the row, no conflicts — and `ne` has a bit per parked row.  The record of the following candidate is
+// loaded in front of the sorted insertion of the current one.  Example, marks in rows 1 (bits 3, 9) and 7 (bit 0), left = 3: the prologue takes row 1
+// as the row fetched ahead (nr = 1, ne = {7}); next(true) makes it current, fetches row 7's words, idx = base1 + 3; step 1 works record base1 + 3
+// while base1 + 9 loads; step 2: the mask of row 1 is empty, row 7 becomes current (ne is empty: nr and its words stay, never taken again),
+// base7 + 0 loads; step 3: left = 1, nothing further is wanted, idx stays and the same record is read again (the load carries no condition, so the
+// compiler does not wait for it where it is issued but behind the insertion).
+// Bench batch, sequential step: grid_search_kernel<16, int> 326 / 320 -> 264 / 259 us per step (two runs each; slowest dispatch now 277, fastest
+// before 297), profiles/r07_knn_grid_select.md.
+// Two records in flight (two slots refilled in turn, 70 registers instead of 60): 265 us, no gain — the compiler waits for the newest load behind the
+// same insertion either way.  Reading the next row's words every step instead of on advance (61 registers): 260 us, inside the run-to-run spread.
+constexpr int GM_NT = 256;               // threads, and queries, per workgroup of the kernel that parks rows: the stride of a lane's words
+template <int R> constexpr int grid_mark_words() { return (2 * R + 1) * (2 * R + 1) * 3 * GM_NT; }
+template <int K, int R>
+__device__ __forceinline__ int grid_mark_select(const GridDesc& d, const int* __restrict__ cell, const SrcGlobal S, float qx, float qy, float qz,
+                                                RegSet<K + 1>& rs, int n1, float& b0, float& b1, int& i0, float& tau) {
+    constexpr int W = 2 * R + 1;
+    static_assert(W * W <= 32, "one bit per row of cells");
+    unsigned* const mk = S.mk;
+    unsigned ne = 0u;                    // rows that hold marks
+    int cy, cz, cnt;
+    const int st = grid_mark_rows<R>(d, cell, S, qx, qy, qz, cy, cz, tau, cnt, [&](int r, unsigned long long m, int s) {
+        if (m) { ne |= 1u << r; mk[(3 * r) * GM_NT] = (unsigned)m; mk[(3 * r + 1) * GM_NT] = (unsigned)(m >> 32); mk[(3 * r + 2) * GM_NT] = (unsigned)s; }
+    });
+    if (st) return st;
+    // fewer than K + 1 marks: a larger block is needed, but the prefix job may still be answerable from the few candidates inside the radius
+    const bool full = cnt >= K + 1;
+    int left = full || n1 > 0 ? cnt : 0;
+    if (full) rs.init();
+    // cnt = the bits set in the parked masks, all rows together: `left` counts the marks not yet taken, so whenever a further one is asked for
+    // (want) either the current mask still has a bit or a non-empty row is left (the row fetched ahead, `nr`, then those of `ne`)
+    if (left > 0) {
+        int nr = __builtin_ctz(ne), r = 0, idx = 0;
+        ne &= ne - 1u;
+        unsigned long long mm = 0ull, nmm; int base = 0, nbase;
+        auto next = [&](bool want) {     // idx: the record of the lane's next mark (want: there is one; otherwise idx stays)
+            const bool adv = want && mm == 0ull;      // the current row is used up: the row fetched ahead becomes the current one
+            if (adv) { mm = nmm; base = nbase; r = nr; }
+            if (adv && ne) {             // ... and the next non-empty row is fetched from LDS while this one is worked off
+                nr = __builtin_ctz(ne); ne &= ne - 1u;
+                nmm = (unsigned long long)mk[(3 * nr) * GM_NT] | ((unsigned long long)mk[(3 * nr + 1) * GM_NT] << 32);
+                nbase = (int)mk[(3 * nr + 2) * GM_NT];
+            }
+            if (want) { idx = base + __ffsll((unsigned long long)mm) - 1; mm &= mm - 1ull; }
+        };
+        nmm = (unsigned long long)mk[(3 * nr) * GM_NT] | ((unsigned long long)mk[(3 * nr + 1) * GM_NT] << 32);
+        nbase = (int)mk[(3 * nr + 2) * GM_NT];
+        next(true);
+        float4 pf = S(cz + r / W - R, cy + r % W - R, idx);
+        do {
+            const float4 p = pf;
+            const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
+            float dist = dx * dx; dist = dist + dy * dy; dist = dist + dz * dz;
+            const int id = __float_as_int(p.w);
+            next(left > 1);
+            pf = S(cz + r / W - R, cy + r % W - R, idx);
+            if (id < n1 && dist < b1) { if (dist < b0) { b1 = b0; b0 = dist; i0 = id; } else b1 = dist; }
+            if (full && dist < rs.worst()) rs.add(dist, id);      // compiled to a branch the wave skips when no lane passes
+        } while (--left > 0);
+    }
+    return full ? 0 : 1;
+}
+
+// The selection with the masks in registers and a loop per row of cells (a wave pays the sum of the rows' largest counts): the LDS-staged form of the
+// first pass keeps it, since the parked rows would halve that kernel's LDS budget and occupancy.
+template <int K, int R>
+__device__ __forceinline__ int grid_mark_select(const GridDesc& d, const int* __restrict__ cell, const SrcLds S, float qx, float qy, float qz,
+                                                RegSet<K + 1>& rs, int n1, float& b0, float& b1, int& i0, float& tau) {
+    constexpr int W = 2 * R + 1;
+    unsigned long long m[W * W]; int rs0[W * W];
 #pragma unroll
-            for (int r = 0; r < W * W; ++r) {
-                unsigned long long mm = m[r];
-                while (mm) {
-                    const int bpos = __ffsll((unsigned long long)mm) - 1;
-                    mm &= mm - 1ull;
-                    const float4 p = S(cz + r / W - R, cy + r % W - R, rs0[r] + bpos);
-                    const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-                    float dist = dx * dx; dist = dist + dy * dy; dist = dist + dz * dz;
-                    if (__float_as_int(p.w) < n1 && dist < b1) { if (dist < b0) { b1 = b0; b0 = dist; i0 = __float_as_int(p.w); } else b1 = dist; }
-                }
-            }
-        }
-        return 1;
-    }
-    rs.init();
+    for (int r = 0; r < W * W; ++r) { m[r] = 0ull; rs0[r] = 0; }
+    int cy, cz, cnt;
+    const int st = grid_mark_rows<R>(d, cell, S, qx, qy, qz, cy, cz, tau, cnt, [&](int r, unsigned long long mr, int s) { m[r] = mr; rs0[r] = s; });
+    if (st) return st;
+    const bool full = cnt >= K + 1;
+    if (!full && n1 <= 0) return 1;
+    if (full) rs.init();
 #pragma unroll
     for (int r = 0; r < W * W; ++r) {
         unsigned long long mm = m[r];
@@ -323,10 +391,10 @@ __device__ __forceinline__ int grid_mark_select(const GridDesc& d, const int* __
             float dist = dx * dx; dist = dist + dy * dy; dist = dist + dz * dz;
             const int id = __float_as_int(p.w);
             if (id < n1 && dist < b1) { if (dist < b0) { b1 = b0; b0 = dist; i0 = id; } else b1 = dist; }
-            if (dist < rs.worst()) rs.add(dist, id);
+            if (full && dist < rs.worst()) rs.add(dist, id);
         }
     }
-    return 0;
+    return full ? 0 : 1;
 }
 
 // first pass: grid.y = job (one support set x one query set x one output block), grid.x = blocks of 256 queries; the 3^3 block.
@@ -360,11 +428,12 @@ __device__ __forceinline__ void grid_search_query(const GridSearchArgs& a, const
 }
 
 template <int K, typename OutT>
-__global__ __launch_bounds__(256) SSDR_WAVES_PER_EU(5) void grid_search_kernel(GridSearchArgs a) {      // 94 registers instead of 106: five waves per SIMD, no spills (six spill: slower)
+__global__ __launch_bounds__(GM_NT) SSDR_WAVES_PER_EU(5) void grid_search_kernel(GridSearchArgs a) {      // five waves per SIMD: six workgroups' parked rows (6 x 27 KiB) do not fit the CU's LDS; registers (60) no longer bound it
+    __shared__ unsigned s_mark[grid_mark_words<1>()];          // each lane's rows of marks (grid_mark_select)
     int bx, by; xcd_tile_map(bx, by);          // a job's support set (one tile's records and cell table) into one XCD's L2
     const int jid = a.job0 + by;
     const GridJob job = a.jobs[jid];
-    const int qi = bx * 256 + (int)threadIdx.x;
+    const int qi = bx * GM_NT + (int)threadIdx.x;
     if (qi >= job.nq) return;
     const GridDesc d = a.desc[job.sup];
     int q = qi; float qx, qy, qz;
@@ -374,7 +443,7 @@ __global__ __launch_bounds__(256) SSDR_WAVES_PER_EU(5) void grid_search_kernel(G
     } else {
         qx = job.qpts[3 * (size_t)q]; qy = job.qpts[3 * (size_t)q + 1]; qz = job.qpts[3 * (size_t)q + 2];
     }
-    grid_search_query<K, OutT>(a, job, jid, d, SrcGlobal{a.sorted + d.pt_off}, q, qx, qy, qz);
+    grid_search_query<K, OutT>(a, job, jid, d, SrcGlobal{a.sorted + d.pt_off, s_mark + threadIdx.x}, q, qx, qy, qz);
 }
 
 // The north_star's form of the first pass, built to be measured beside the one above: the workgroup's 256 cell-sorted queries touch a few rows of
@@ -595,11 +664,11 @@ int grid_search(const GridForest& g, int job0, int njobs, int max_nq, int K, boo
     if (first) {
         ProfScope prof(K == 16 ? "grid_search_kernel<16>" : "grid_search_kernel<1>", s, prof_bytes);
         if (K == 16) {
-            if (out_i64) { if (lds_form) hipLaunchKernelGGL((grid_search_lds_kernel<16, int64_t>), grid, dim3(256), 0, s, a); else hipLaunchKernelGGL((grid_search_kernel<16, int64_t>), grid, dim3(256), 0, s, a); }
-            else { if (lds_form) hipLaunchKernelGGL((grid_search_lds_kernel<16, int32_t>), grid, dim3(256), 0, s, a); else hipLaunchKernelGGL((grid_search_kernel<16, int32_t>), grid, dim3(256), 0, s, a); }
+            if (out_i64) { if (lds_form) hipLaunchKernelGGL((grid_search_lds_kernel<16, int64_t>), grid, dim3(GM_NT), 0, s, a); else hipLaunchKernelGGL((grid_search_kernel<16, int64_t>), grid, dim3(GM_NT), 0, s, a); }
+            else { if (lds_form) hipLaunchKernelGGL((grid_search_lds_kernel<16, int32_t>), grid, dim3(GM_NT), 0, s, a); else hipLaunchKernelGGL((grid_search_kernel<16, int32_t>), grid, dim3(GM_NT), 0, s, a); }
         } else {
-            if (out_i64) hipLaunchKernelGGL((grid_search_kernel<1, int64_t>), grid, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((grid_search_kernel<1, int32_t>), grid, dim3(256), 0, s, a);
+            if (out_i64) hipLaunchKernelGGL((grid_search_kernel<1, int64_t>), grid, dim3(GM_NT), 0, s, a);
+            else hipLaunchKernelGGL((grid_search_kernel<1, int32_t>), grid, dim3(GM_NT), 0, s, a);
         }
     }
     {
