@@ -537,6 +537,41 @@ int ssdr_oracle_label_dev(const int32_t* d_gt, const int32_t* d_pred_class, size
 int ssdr_oracle_label_items_dev(const int32_t* d_result, int layout, size_t max_select, const int32_t* d_order, size_t S, const uint8_t* d_skip,
                                 const int32_t* d_sp_cloud, size_t num_clouds, int32_t* d_items, size_t max_items, int32_t* d_n_items, int32_t* d_cloud_key,
                                 void* stream);
+/* ---- the same chain in two halves, for a round whose clouds are sharded over `world` ranks -------------------------------------------------------------
+ * The walk is a prefix sum over costs that depend on the item alone, so: every rank judges its own items (verdict half), the fixed-size verdict records
+ * are all-gathered, and every rank sorts all records by their 64-bit walk key, runs the same scan over them and applies its own (walk half).  Both
+ * entries are enqueue-only with per-stream scratch.  A record (SSDR_LABEL_RECORD_BYTES = 80, a multiple of 16 so that gathered slices stay aligned):
+ *    0 uint64 key        the walk key (live keys are unique over all ranks; all ones: a dead slot beyond the rank's live count, cost 0, sorts last)
+ *    8 int32  pos        the slot among the rank's items
+ *   12 int32  kind       0 skipped (fewer than min_size points / no such region), 1 whole region, 2 split, 3 ignored
+ *   16 int32  lab, 20 cost (clicks), 24 nent (class-list entries), 28 subp (points of the labelled sub-regions), 32 len (points of the region)
+ *   36 uint32 smask      the predicted classes whose sub-region is labelled
+ *   40 uint8  sublab[32] their labels (0 where the mask is clear)
+ *   72 int32  status     the bits (1, 2, 4 above) the rank's verdict half raised; 76: zero
+ * ssdr_oracle_label_verdict_dev: d_items [max_items] are LOCAL superpoint ids, *d_n_items of them live, d_keys [max_items] their walk keys (cloud key in
+ * the high half, position in pick order in the low half); same wave / workgroup forms, 256-point boundary and max_region shortcut as above; writes
+ * d_records [max_items].
+ * ssdr_oracle_label_walk_dev: d_records [world * max_items] rank-major (what the all-gather of the verdict halves' buffers gives); the other arrays are
+ * this rank's.  Writes the WHOLE class list in walk order (identical on every rank), d_out [12] with the meaning above (counters, entries, budget left and
+ * the status over all ranks; words 10 and 11 count all ranks' regions per form) and *d_budget; applies only the records of `rank`: d_mask / d_label,
+ * d_used [max_items], d_labeled [S]; d_walk_pos [max_items]: every own item's position in the global walk, -1 when the walk does not reach it.
+ * With world = 1 and the keys (first appearance or cloud key) << 32 | position every output equals ssdr_oracle_label_dev's (d_walk_pos inverts d_proc_order). */
+#define SSDR_LABEL_RECORD_BYTES 80
+int ssdr_oracle_label_verdict_dev(const int32_t* d_gt, const int32_t* d_pred_class, size_t n, const int32_t* d_sp_off, const int32_t* d_sp_pts, size_t S,
+                                  const int32_t* d_items, const int32_t* d_n_items, size_t max_items, const uint64_t* d_keys, size_t max_region, int num_labels,
+                                  int num_classes, int mode, double threshold, int64_t min_size, void* d_records, void* stream);
+int ssdr_oracle_label_walk_dev(const void* d_records, int rank, int world, const int32_t* d_pred_class, size_t n, const int32_t* d_sp_off, const int32_t* d_sp_pts, size_t S,
+                               const int32_t* d_items, const int32_t* d_n_items, size_t max_items, size_t max_region, int num_classes, int64_t* d_budget, float* d_mask,
+                               float* d_label, uint8_t* d_used, uint8_t* d_labeled, int32_t* d_class_out, size_t class_cap, int32_t* d_walk_pos, int64_t* d_out,
+                               void* stream);
+/* The walk keys of a sharded round, on the device.  Global superpoint id = rank * Smax + local id; d_gcloud [world * Smax] = every global region's global
+ * cloud (below num_gclouds; -1: padding).  d_picks given (fps / k-center: the picks [n_picks] index the replicated global candidate list d_cand
+ * [*d_n_cand <= cand_cap]): a cloud's key is its first appearance among ALL picks; the picks whose region lives on `rank` become d_items (local ids, pick
+ * order) / *d_n_items with the global pick position as the low half.  d_picks NULL (edcd / topk: d_items / *d_n_items are the rank's own picks): the key
+ * is d_cloud_key [num_gclouds] of the item's cloud (ssdr_oracle_label_items_dev over the global ranking), the low half the position among the items. */
+int ssdr_oracle_label_keys_dev(const int32_t* d_picks, size_t n_picks, const int32_t* d_n_cand, const int32_t* d_cand, size_t cand_cap, const int32_t* d_gcloud, size_t Smax,
+                               size_t num_gclouds, int rank, int world, const int32_t* d_cloud_key, int32_t* d_items, int32_t* d_n_items, size_t max_items, uint64_t* d_keys,
+                               void* stream);
 /* kCenterGreedy.select_batch_ (kcenterGreedy.py:84-128) with direct float64 Euclidean distances */
 int ssdr_kcenter_dev(const double* d_feat, size_t n, int feat_dim, const int32_t* d_already_selected, size_t n_already, size_t count,
                      int32_t* d_out, void* stream);

@@ -14,6 +14,8 @@
 //   4. apply    processed items write their points, class entries, used flag and labelled-mask byte.  A region picked twice pays twice and writes
 //               the same values twice.
 // Nothing waits on the host; the scratch is per stream.
+// A sharded round runs the same chain in two halves around one all-gather (further down): verdicts of a rank's own items packed into fixed-size
+// records, then order / scan / apply over the records of all ranks.
 #include "ssdr_internal.hpp"
 #include "block_prims.hpp"
 
@@ -266,6 +268,22 @@ __global__ __launch_bounds__(1024) void label_scan(LabelArgs a, long long* budge
 // ---- 4. apply ----------------------------------------------------------------------------------------------------------------------------------
 struct LabelOut { float* mask; float* label; unsigned char* used; unsigned char* labeled; int* class_out; long long class_cap; int* proc_order; };
 
+// (the record path's: apply_item of the one-call chain keeps its own loops)
+// thread t of nt writes the points [lo, lo + n) of a region judged `kind` (1: whole, 2: split by predicted class with the sub-regions' labels sl)
+__device__ __forceinline__ void apply_points(const int* __restrict__ sp_pts, const int* __restrict__ pred, long long npts, int nc, const LabelOut& o, int kind, int lab,
+                                             unsigned sm, const unsigned char* sl, int lo, int n, int t, int nt) {
+    if (kind == 1) {
+        const float v = (float)lab;
+        for (int i = t; i < n; i += nt) { const int p = sp_pts[lo + i]; if (p >= 0 && p < npts) { o.mask[p] = 1.0f; o.label[p] = v; } }
+    } else if (kind == 2) {
+        for (int i = t; i < n; i += nt) {
+            const int p = sp_pts[lo + i];
+            if (p < 0 || p >= npts) continue;
+            const int c = pred[p];
+            if (c >= 0 && c < nc && ((sm >> c) & 1u)) { o.mask[p] = 1.0f; o.label[p] = (float)sl[c]; }
+        }
+    }
+}
 // thread t of nt working on position j
 __device__ __forceinline__ void apply_item(const LabelArgs& a, const LabelOut& o, int j, int t, int nt) {
     const int e = a.eoff[j], kind = a.kind[j];
@@ -304,6 +322,204 @@ __global__ __launch_bounds__(256) void label_apply_wave(LabelArgs a, LabelOut o)
 __global__ __launch_bounds__(256) void label_apply_block(LabelArgs a, LabelOut o) {
     const int nb = a.cnt[0];
     for (int b = blockIdx.x; b < nb; b += gridDim.x) apply_item(a, o, a.big[b], threadIdx.x, 256);
+}
+
+// ---- the chain in two halves: a sharded round ----------------------------------------------------------------------------------------------------
+// A rank judges its own items (verdict half) and packs one fixed-size record per item slot; the records of all ranks are gathered; every rank sorts
+// them by their walk key, runs the scan above over ALL of them (costs depend on the item alone, so the replicated prefix sum is the sequential walk)
+// and applies its own (walk half).  Dead slots (beyond a rank's live count) carry an all-ones key and cost nothing: they sort last.
+struct LabelRecord {
+    unsigned long long key;                    // 0: cloud key << 32 | position in pick order
+    int pos, kind, lab, cost, nent, subp, len; // 8: the slot among the rank's items; 12 .. 35: the verdict
+    unsigned smask;                            // 36: the sub-regions (predicted classes) that are labelled
+    unsigned char sublab[32];                  // 40: their labels (0 where the mask is clear)
+    int status, pad;                           // 72: the status bits the rank's verdict half raised
+};
+static_assert(sizeof(LabelRecord) == SSDR_LABEL_RECORD_BYTES && SSDR_LABEL_RECORD_BYTES % 16 == 0, "record layout (ssdr_al.h)");
+constexpr unsigned long long LB_DEAD_KEY = ~0ull;
+
+__global__ __launch_bounds__(256) void label_ident(LabelArgs a, unsigned* ord) {
+    const int M = item_count(a);
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < a.max_items; i += gridDim.x * 256) {
+        ord[i] = (unsigned)i;
+        if (i < M && item_cloud(a, a.items[i]) < 0) atomicOr(&a.cnt[1], (int)LB_ST_ITEM);
+    }
+}
+__global__ __launch_bounds__(256) void label_pack(LabelArgs a, const unsigned long long* __restrict__ keys, LabelRecord* rec) {
+    const int M = item_count(a), st = a.cnt[1];
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < a.max_items; i += gridDim.x * 256) {
+        LabelRecord r;
+        const bool live = i < M;
+        const int kind = live ? a.kind[i] : 0;
+        r.key = live ? keys[i] : LB_DEAD_KEY; r.pos = i; r.kind = kind;
+        r.lab = live ? a.lab[i] : 0; r.cost = live ? a.cost[i] : 0; r.nent = live ? a.nent[i] : 0; r.subp = live ? a.subp[i] : 0; r.len = live ? a.len[i] : 0;
+        r.smask = kind == 2 ? a.smask[i] : 0u;
+#pragma unroll
+        for (int k = 0; k < 32; ++k) r.sublab[k] = (r.smask >> k) & 1u ? a.sublab[(size_t)i * 32 + k] : (unsigned char)0;
+        r.status = st; r.pad = 0;
+        rec[i] = r;
+    }
+}
+
+struct WalkArgs {
+    const LabelRecord* rec; int total, max_items, rank;                  // all ranks' records, rank-major
+    const unsigned* ord;                                                   // the record at every position of the walk
+    const int* pred; long long n; const int* sp_off; const int* sp_pts; int S, nc;
+    const int* items; const int* n_items;                                // this rank's
+    int* eoff; int* big; int* cnt; int* walk_pos;
+};
+__global__ __launch_bounds__(256) void label_record_keys(WalkArgs a, unsigned long long* keys, unsigned* vals) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < a.total; i += gridDim.x * 256) {
+        keys[i] = a.rec[i].key; vals[i] = (unsigned)i;
+        if (i % a.max_items == 0 && a.rec[i].status) atomicOr(&a.cnt[1], a.rec[i].status & (LB_ST_LABEL | LB_ST_CLASS | LB_ST_ITEM));      // a rank's bits ride in its records
+    }
+}
+// label_scan over all ranks' records through their sorted order (dead records: no cost, no entry, kind 0)
+__global__ __launch_bounds__(1024) void label_scan_records(WalkArgs a, long long* budget_io, long long class_cap, long long* out) {
+    __shared__ long long s_c[16], s_e[16], s_r[16][8];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int M = a.total;
+    const long long budget = *budget_io;
+    if (tid == 0) { out[6] = 0; out[7] = budget; }
+    long long runc = 0, rune = 0, ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int base = 0; base < M; base += 1024) {
+        const int j = base + tid;
+        const long long cost = j < M ? max(a.rec[a.ord[j]].cost, 0) : 0, ne = j < M ? max(a.rec[a.ord[j]].nent, 0) : 0;
+        long long ic = cost, ie = ne;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const long long tc = __shfl_up(ic, (unsigned)o), te = __shfl_up(ie, (unsigned)o);
+            if (lane >= o) { ic += tc; ie += te; }
+        }
+        if (lane == 63) { s_c[w] = ic; s_e[w] = ie; }
+        __syncthreads();                    // (also orders thread 0's defaults before the last processed item's totals)
+        long long pc = 0, pe = 0, tc = 0, te = 0;
+        for (int q = 0; q < 16; ++q) { if (q < w) { pc += s_c[q]; pe += s_e[q]; } tc += s_c[q]; te += s_e[q]; }
+        const long long exc = runc + pc + ic - cost, exe = rune + pe + ie - ne;
+        if (j < M) {
+            const bool proc = exc < budget;                             // budget["click"] > 0 when the walk reaches the item
+            const LabelRecord& q = a.rec[a.ord[j]];
+            const int kind = q.kind;
+            a.eoff[j] = proc ? (int)min(exe, (long long)0x7fffffff) : -1;
+            if (kind) ctr[q.len > LB_WAVE_MAX ? 7 : 6] += 1;
+            if (proc) {
+                if (kind == 1) { ctr[0] += 1; ctr[1] += q.len; }
+                if (kind == 2) { ctr[2] += ne; ctr[3] += q.subp; ctr[4] += 1; }
+                if (kind == 3) ctr[5] += 1;
+                if (j == M - 1 || exc + cost >= budget) {               // the last item the walk processes: the totals
+                    out[6] = exe + ne; out[7] = budget - (exc + cost); *budget_io = budget - (exc + cost);
+                    if (exe + ne > class_cap) atomicOr(&a.cnt[1], (int)LB_ST_CAP);
+                }
+            }
+        }
+        runc += tc; rune += te;
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) { const long long v = wave_sum_ll(ctr[q]); if (lane == 0) s_r[w][q] = v; }
+    __syncthreads();
+    if (tid == 0) {
+        long long t[8];
+        for (int c = 0; c < 8; ++c) { t[c] = 0; for (int q = 0; q < 16; ++q) t[c] += s_r[q][c]; }
+        for (int c = 0; c < 6; ++c) out[c] = t[c];
+        out[8] = a.cnt[1]; out[9] = t[0] + t[4] + t[5]; out[10] = t[6]; out[11] = t[7];
+    }
+}
+// the class list from ALL records (identical on every rank); this rank's own records: walk position, used flag, labelled byte, points
+__device__ __forceinline__ bool walk_own(const WalkArgs& a, unsigned r, int& slot, int& sp, int& lo, int& n) {
+    slot = (int)(r % (unsigned)a.max_items);
+    if ((int)(r / (unsigned)a.max_items) != a.rank || slot >= max(0, min(*a.n_items, a.max_items))) return false;
+    sp = a.items[slot];
+    if (sp < 0 || sp >= a.S) return false;
+    lo = a.sp_off[sp]; n = a.sp_off[sp + 1] - lo;
+    return true;
+}
+__global__ __launch_bounds__(256) void label_walk_apply_wave(WalkArgs a, LabelOut o) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int j = blockIdx.x * 4 + w; j < a.total; j += gridDim.x * 4) {
+        const unsigned r = a.ord[j];
+        const LabelRecord& q = a.rec[r];
+        const int e = a.eoff[j];
+        if (e < 0 || q.key == LB_DEAD_KEY) continue;
+        int slot, sp, lo, n;
+        const bool own = walk_own(a, r, slot, sp, lo, n);
+        if (lane == 0) {
+            if (own) a.walk_pos[slot] = j;
+            if ((long long)e + max(q.nent, 0) <= o.class_cap) {           // (all of an item's entries or none, as the one-call chain)
+                if (q.kind == 1 && e < o.class_cap) o.class_out[e] = q.lab;
+                if (q.kind == 2) { int c = 0; for (int k = 0; k < 32; ++k) if ((q.smask >> k) & 1u) { if ((long long)e + c < o.class_cap) o.class_out[e + c] = q.sublab[k]; ++c; } }
+            }
+        }
+        if (!own || (q.kind != 1 && q.kind != 2 && q.kind != 3)) continue;
+        if (lane == 0) { o.used[slot] = 1; o.labeled[sp] = 1; }
+        if (q.kind == 3 || (q.kind == 2 && !a.pred)) continue;
+        if (n > LB_WAVE_MAX) { if (lane == 0) a.big[atomicAdd(&a.cnt[0], 1)] = j; continue; }
+        apply_points(a.sp_pts, a.pred, a.n, a.nc, o, q.kind, q.lab, q.smask, q.sublab, lo, n, lane, 64);
+    }
+}
+__global__ __launch_bounds__(256) void label_walk_apply_block(WalkArgs a, LabelOut o) {
+    const int nb = min(a.cnt[0], a.max_items);
+    for (int b = blockIdx.x; b < nb; b += gridDim.x) {
+        const unsigned r = a.ord[a.big[b]];
+        const LabelRecord& q = a.rec[r];
+        int slot, sp, lo, n;
+        if (walk_own(a, r, slot, sp, lo, n)) apply_points(a.sp_pts, a.pred, a.n, a.nc, o, q.kind, q.lab, q.smask, q.sublab, lo, n, threadIdx.x, 256);
+    }
+}
+
+// ---- walk keys of a sharded round: cloud key << 32 | position in pick order ----------------------------------------------------------------------------
+// fps / k-center: the picks (indices into the global candidate list, both replicated); a cloud's key is its first appearance among ALL picks
+__global__ __launch_bounds__(256) void label_pick_first(const int* __restrict__ picks, int n_picks, const int* __restrict__ n_cand, const int* __restrict__ cand, int cand_cap,
+                                                        const int* __restrict__ gcloud, long long G, int NB, int* first) {
+    const int ng = max(0, min(*n_cand, cand_cap));
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n_picks; i += gridDim.x * 256) {
+        const int s = picks[i];
+        if (s < 0 || s >= ng) continue;
+        const int g = cand[s];
+        if (g < 0 || g >= G) continue;
+        const int c = gcloud[g];
+        if (c >= 0 && c < NB) atomicMin(&first[c], i);
+    }
+}
+// ... and this rank's share of them, in pick order: an ordered compaction by one workgroup
+__global__ __launch_bounds__(1024) void label_own_picks(const int* __restrict__ picks, int n_picks, const int* __restrict__ n_cand, const int* __restrict__ cand, int cand_cap,
+                                                        const int* __restrict__ gcloud, long long G, int NB, const int* __restrict__ first, int rank, int Smax,
+                                                        int max_items, int* items, int* n_items, unsigned long long* keys) {
+    __shared__ int s_w[16];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int ng = max(0, min(*n_cand, cand_cap));
+    int run = 0;
+    for (int base = 0; base < n_picks; base += 1024) {
+        const int i = base + tid;
+        int g = -1;
+        if (i < n_picks) { const int s = picks[i]; if (s >= 0 && s < ng) g = cand[s]; }
+        const bool mine = g >= 0 && g < G && g / Smax == rank;
+        const unsigned long long b = __ballot(mine);
+        if (lane == 0) s_w[w] = __popcll(b);
+        __syncthreads();
+        int before = run, tot = 0;
+        for (int q = 0; q < 16; ++q) { if (q < w) before += s_w[q]; tot += s_w[q]; }
+        const int at = before + __popcll(b & ((1ull << lane) - 1ull));
+        if (mine && at < max_items) {
+            const int c = gcloud[g];
+            const unsigned long long hi = c >= 0 && c < NB ? (unsigned long long)(unsigned)max(first[c], 0) : 0x7fffffffull;
+            items[at] = g - rank * Smax; keys[at] = (hi << 32) | (unsigned long long)(unsigned)i;
+        }
+        run += tot;
+        __syncthreads();
+    }
+    if (tid == 0) *n_items = min(run, max_items);
+}
+// edcd / topk: a rank holds its own picks; the cloud key is the caller's (per global cloud), the low half the position among the rank's picks
+__global__ __launch_bounds__(256) void label_item_keys(const int* __restrict__ items, const int* __restrict__ n_items, int max_items, const int* __restrict__ gcloud, int rank,
+                                                       int Smax, int NB, const int* __restrict__ cloud_key, unsigned long long* keys) {
+    const int M = max(0, min(*n_items, max_items));
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < M; i += gridDim.x * 256) {
+        const int sp = items[i];
+        const int c = sp >= 0 && sp < Smax ? gcloud[(long long)rank * Smax + sp] : -1;
+        const unsigned long long hi = c >= 0 && c < NB ? (unsigned long long)(unsigned)max(cloud_key[c], 0) : 0x7fffffffull;
+        keys[i] = (hi << 32) | (unsigned long long)(unsigned)i;
+    }
 }
 
 // ---- the picks of a one-call selection chain as items --------------------------------------------------------------------------------------------
@@ -415,6 +631,109 @@ int ssdr_oracle_label_items_dev(const int32_t* d_result, int layout, size_t max_
     if (d_cloud_key && num_clouds) {
         SSDR_HIP(hipMemsetAsync(d_cloud_key, 0x7f, 4 * num_clouds, s));
         if (S) hipLaunchKernelGGL(label_rank_key, dim3(grid_of(S, 256, 16)), dim3(256), 0, s, d_order, (int)S, d_skip, d_sp_cloud, (int)num_clouds, d_cloud_key);
+    }
+    SSDR_HIP(hipGetLastError());
+    return SSDR_OK;
+}
+
+int ssdr_oracle_label_verdict_dev(const int32_t* d_gt, const int32_t* d_pred_class, size_t n, const int32_t* d_sp_off, const int32_t* d_sp_pts, size_t S,
+                                  const int32_t* d_items, const int32_t* d_n_items, size_t max_items, const uint64_t* d_keys, size_t max_region, int num_labels,
+                                  int num_classes, int mode, double threshold, int64_t min_size, void* d_records, void* stream) {
+    if (mode != SSDR_LABEL_DOMINANT && mode != SSDR_LABEL_NAIL) { set_error("oracle_label_verdict: unknown oracle mode %d (0: dominant, 1: NAIL)", mode); return SSDR_ERR_INVALID; }
+    if (!d_gt || !d_sp_off || !d_sp_pts || !d_n_items || (max_items && (!d_items || !d_keys || !d_records)) || (mode == SSDR_LABEL_NAIL && !d_pred_class) || num_labels < 1 ||
+        num_labels > 64 || num_classes < 1 || num_classes > 32 || max_items > LB_MAX_ITEMS || S > 0x7ffffff0 || n > 0x7ffffff0 || !(threshold == threshold)) {
+        set_error("oracle_label_verdict: bad arguments (num_labels <= 64, num_classes <= 32, at most 2^22 items)"); return SSDR_ERR_INVALID;
+    }
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream); LabelState& Q = lst(s);
+    const size_t M = max_items, Mp = std::max<size_t>(M, 1);
+    if (!M) return SSDR_OK;
+    SSDR_TRY(Q.vals.reserve(4 * Mp)); SSDR_TRY(Q.verdict.reserve(4 * 8 * Mp)); SSDR_TRY(Q.sublab.reserve(32 * Mp)); SSDR_TRY(Q.big.reserve(4 * Mp)); SSDR_TRY(Q.cnt.reserve(64));
+    SSDR_TRY(Q.first.reserve(4 * std::max<size_t>(S, 1)));      // the verdict kernels ask for an item's cloud: here every region is cloud 0 of one
+    SSDR_HIP(hipMemsetAsync(Q.first.p, 0, 4 * std::max<size_t>(S, 1), s));
+    int* v = Q.verdict.as<int>();
+    LabelArgs a{d_gt, d_pred_class, (long long)n, d_sp_off, d_sp_pts, Q.first.as<int>(), (int)S, 1, d_items, d_n_items, (int)M,
+                num_labels, num_classes, mode == SSDR_LABEL_NAIL ? 1 : 0, threshold, (long long)min_size,
+                Q.vals.as<unsigned>(), v, v + Mp, v + 2 * Mp, v + 3 * Mp, v + 4 * Mp, v + 5 * Mp, v + 6 * Mp, reinterpret_cast<unsigned*>(v + 7 * Mp),
+                Q.sublab.as<unsigned char>(), Q.big.as<int>(), Q.cnt.as<int>()};
+    SSDR_HIP(hipMemsetAsync(Q.cnt.p, 0, 64, s));
+    hipLaunchKernelGGL(label_ident, dim3(grid_of(M, 256, 16)), dim3(256), 0, s, a, Q.vals.as<unsigned>());
+    {
+        ProfScope prof("label_form:wave", s, 0.0);
+        hipLaunchKernelGGL(label_verdict_wave, dim3(grid_of(M, 4, 16)), dim3(256), 0, s, a);
+    }
+    if (max_region == 0 || max_region > (size_t)LB_WAVE_MAX) {
+        ProfScope prof("label_form:block", s, 0.0);
+        hipLaunchKernelGGL(label_verdict_block, dim3(grid_of(M, 1, 4)), dim3(256), 0, s, a);
+    }
+    {
+        ProfScope prof("label_pack", s, (double)SSDR_LABEL_RECORD_BYTES * (double)M);
+        hipLaunchKernelGGL(label_pack, dim3(grid_of(M, 256, 16)), dim3(256), 0, s, a, (const unsigned long long*)d_keys, reinterpret_cast<LabelRecord*>(d_records));
+    }
+    SSDR_HIP(hipGetLastError());
+    return SSDR_OK;
+}
+
+int ssdr_oracle_label_walk_dev(const void* d_records, int rank, int world, const int32_t* d_pred_class, size_t n, const int32_t* d_sp_off, const int32_t* d_sp_pts, size_t S,
+                               const int32_t* d_items, const int32_t* d_n_items, size_t max_items, size_t max_region, int num_classes, int64_t* d_budget, float* d_mask,
+                               float* d_label, uint8_t* d_used, uint8_t* d_labeled, int32_t* d_class_out, size_t class_cap, int32_t* d_walk_pos, int64_t* d_out,
+                               void* stream) {
+    if (world < 1 || world > 4096 || rank < 0 || rank >= world || !d_sp_off || !d_sp_pts || !d_n_items || !d_budget || !d_mask || !d_label || !d_used || !d_labeled ||
+        !d_class_out || !d_out || !d_walk_pos || (max_items && (!d_items || !d_records)) || num_classes < 1 || num_classes > 32 || max_items > LB_MAX_ITEMS ||
+        (size_t)world * max_items > ((size_t)1 << 26) || S > 0x7ffffff0 || n > 0x7ffffff0) {
+        set_error("oracle_label_walk: bad arguments (0 <= rank < world, num_classes <= 32, at most 2^22 items per rank and 2^26 records)"); return SSDR_ERR_INVALID;
+    }
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream); LabelState& Q = lst(s);
+    const size_t M = max_items, T = (size_t)world * M, Tp = std::max<size_t>(T, 1);
+    SSDR_TRY(Q.keys.reserve(8 * Tp)); SSDR_TRY(Q.vals.reserve(4 * Tp)); SSDR_TRY(Q.verdict.reserve(4 * Tp)); SSDR_TRY(Q.big.reserve(4 * std::max<size_t>(M, 1))); SSDR_TRY(Q.cnt.reserve(64));
+    WalkArgs a{reinterpret_cast<const LabelRecord*>(d_records), (int)T, (int)M, rank, Q.vals.as<unsigned>(), d_pred_class, (long long)n, d_sp_off, d_sp_pts, (int)S, num_classes,
+               d_items, d_n_items, Q.verdict.as<int>(), Q.big.as<int>(), Q.cnt.as<int>(), d_walk_pos};
+    LabelOut o{d_mask, d_label, d_used, d_labeled, d_class_out, (long long)std::min<size_t>(class_cap, (size_t)1 << 40), nullptr};
+    SSDR_HIP(hipMemsetAsync(Q.cnt.p, 0, 64, s));
+    if (T) {
+        SSDR_HIP(hipMemsetAsync(d_used, 0, M, s));
+        SSDR_HIP(hipMemsetAsync(d_walk_pos, 0xff, 4 * M, s));
+        ProfScope prof("label_order", s, 16.0 * (double)T);
+        hipLaunchKernelGGL(label_record_keys, dim3(grid_of(T, 256, 16)), dim3(256), 0, s, a, Q.keys.as<unsigned long long>(), Q.vals.as<unsigned>());
+        Q.sorter.wide_high = true;            // the cloud keys vary above bit 32: from 16 384 records on, wide passes there too (the one-call chain sorts 31 bits)
+        SSDR_TRY(Q.sorter.sort(Q.keys.as<uint64_t>(), Q.vals.as<uint32_t>(), (int)T, nullptr, s, 64));
+    }
+    {
+        ProfScope prof("label_scan", s, 0.0);
+        hipLaunchKernelGGL(label_scan_records, dim3(1), dim3(1024), 0, s, a, (long long*)d_budget, o.class_cap, (long long*)d_out);
+    }
+    if (T) {
+        ProfScope prof("label_apply", s, 0.0);
+        hipLaunchKernelGGL(label_walk_apply_wave, dim3(grid_of(T, 4, 16)), dim3(256), 0, s, a, o);
+        if (max_region == 0 || max_region > (size_t)LB_WAVE_MAX) hipLaunchKernelGGL(label_walk_apply_block, dim3(grid_of(M, 1, 4)), dim3(256), 0, s, a, o);
+    }
+    SSDR_HIP(hipGetLastError());
+    return SSDR_OK;
+}
+
+int ssdr_oracle_label_keys_dev(const int32_t* d_picks, size_t n_picks, const int32_t* d_n_cand, const int32_t* d_cand, size_t cand_cap, const int32_t* d_gcloud, size_t Smax,
+                               size_t num_gclouds, int rank, int world, const int32_t* d_cloud_key, int32_t* d_items, int32_t* d_n_items, size_t max_items, uint64_t* d_keys,
+                               void* stream) {
+    if (world < 1 || world > 4096 || rank < 0 || rank >= world || !d_gcloud || !d_n_items || (max_items && (!d_items || !d_keys)) || max_items > LB_MAX_ITEMS || Smax < 1 ||
+        (size_t)world * Smax > 0x7ffffff0 || num_gclouds < 1 || num_gclouds > 0x7ffffff0 || n_picks > 0x7ffffff0 || cand_cap > 0x7ffffff0 ||
+        (d_picks ? (!d_n_cand || !d_cand) : !d_cloud_key)) {
+        set_error("oracle_label_keys: bad arguments (the picks with the candidate list, or a key per global cloud)"); return SSDR_ERR_INVALID;
+    }
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream); LabelState& Q = lst(s);
+    ProfScope prof("label_keys", s, 0.0);
+    if (d_picks) {
+        SSDR_TRY(Q.first.reserve(4 * num_gclouds));
+        SSDR_HIP(hipMemsetAsync(Q.first.p, 0x7f, 4 * num_gclouds, s));
+        const long long G = (long long)world * (long long)Smax;
+        if (n_picks) hipLaunchKernelGGL(label_pick_first, dim3(grid_of(n_picks, 256, 16)), dim3(256), 0, s, d_picks, (int)n_picks, d_n_cand, d_cand, (int)cand_cap, d_gcloud, G,
+                                        (int)num_gclouds, Q.first.as<int>());
+        hipLaunchKernelGGL(label_own_picks, dim3(1), dim3(1024), 0, s, d_picks, (int)n_picks, d_n_cand, d_cand, (int)cand_cap, d_gcloud, G, (int)num_gclouds,
+                           (const int*)Q.first.as<int>(), rank, (int)Smax, (int)max_items, d_items, d_n_items, (unsigned long long*)d_keys);
+    } else if (max_items) {
+        hipLaunchKernelGGL(label_item_keys, dim3(grid_of(max_items, 256, 16)), dim3(256), 0, s, d_items, d_n_items, (int)max_items, d_gcloud, rank, (int)Smax, (int)num_gclouds,
+                           d_cloud_key, (unsigned long long*)d_keys);
     }
     SSDR_HIP(hipGetLastError());
     return SSDR_OK;

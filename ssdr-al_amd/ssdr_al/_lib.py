@@ -15,6 +15,7 @@ DEFAULT_PATH = os.path.join(_PKG, "libssdr_al.so")
 
 SSDR_OK = 0
 ORDER_REFERENCE, ORDER_KEY = 0, 1
+LABEL_RECORD_BYTES = 80      # SSDR_LABEL_RECORD_BYTES: one verdict record of the sharded labelling
 
 _lib = None
 _forced_path = None
@@ -108,6 +109,9 @@ def lib():
         L.ssdr_topk_regions_dev.argtypes = [vp, sz, vp, sz, sz, sz, vp, vp, vp]
         L.ssdr_oracle_label_dev.argtypes = [vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, sz, vp, sz, i32, i32, i32, f64, C.c_int64, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]
         L.ssdr_oracle_label_items_dev.argtypes = [vp, i32, sz, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp]
+        L.ssdr_oracle_label_verdict_dev.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, sz, i32, i32, i32, f64, C.c_int64, vp, vp]
+        L.ssdr_oracle_label_walk_dev.argtypes = [vp, i32, i32, vp, sz, vp, vp, sz, vp, vp, sz, sz, i32, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]
+        L.ssdr_oracle_label_keys_dev.argtypes = [vp, sz, vp, vp, sz, vp, sz, sz, i32, i32, vp, vp, vp, sz, vp, vp]
         L.ssdr_gcn_fps_sharded_local_dev.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, i32, i32, sz, sz, sz, i32, i32, sz, sz, sz, sz, sz, vp, vp, vp]
         L.ssdr_event_create.argtypes = [C.POINTER(vp)]; L.ssdr_event_record.argtypes = [vp, vp]; L.ssdr_stream_wait_event.argtypes = [vp, vp]; L.ssdr_event_destroy.argtypes = [vp]
         L.ssdr_select_set_chamfer_mode.argtypes = [i32]

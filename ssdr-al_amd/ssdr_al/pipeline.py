@@ -431,7 +431,7 @@ class HotPath:
             dev.update(t_result=DevArray((8 + max(min(batch, self.S), 1),), np.int32))
         self._dist = dict(dev=dev, comm=comm, Smax=Smax, Bmax=Bmax, valid=lab == 0, gcloud=gcloud, room=room, spin=spin, batch=batch,
                           S_total=int(S_all[:, 0].sum()), n_pop=int(nvalid_all.sum()), nu_max=int(min(2 * batch, Smax)),
-                          nlab=nlab,
+                          nlab=nlab, nvalid_all=nvalid_all, d_gcloud=DevArray.from_host(gcloud.astype(np.int32)),      # (the sharded labelling: every global region's global cloud)
                           d_lab=DevArray.from_host(self.skip_mask.astype(np.uint8)),
                           d_masked=DevArray((Smax,), np.float64), d_all=DevArray((W * Smax,), np.float64), d_ord=DevArray((W * Smax,), np.int32))
         return self._dist
@@ -565,6 +565,7 @@ class HotPath:
         else:       # every rank derives the global candidate list from the global ranking, then keeps its own rows
             D = self.global_order
             gcand, gcloud, sampling_batch = self._candidates(D["d_ord"].to_host(st), D["valid"], D["gcloud"], D["batch"])
+            self._gcand_h = gcand                                # (label_selected(comm=): the picks index this list)
             r_of = gcand // D["Smax"]
             counts_r = np.bincount(r_of, minlength=comm.world)
             mine = r_of == comm.rank
@@ -701,6 +702,7 @@ class HotPath:
             order, valid, cloud, batch, sub_c, sub_s = D["d_ord"].to_host(st), D["valid"], D["gcloud"], D["batch"], comm.rank * D["Bmax"], comm.rank * D["Smax"]
             room, spin = D["room"], D["spin"]
         order = np.asarray(order, np.int64)
+        self._gorder_h = order
         if not edcd:                          # the top: the first batch_size regions of the population in rank order, this rank's own kept
             top = order[valid[order]][: batch]
             top = top[(top >= sub_s) & (top < sub_s + self.S)]
@@ -765,7 +767,7 @@ class HotPath:
             self._comb_dev, self._comb_n = V["d_glob"], n_g + (V["n_lab_all"] if self.selector == "kcenter" else 0)
             if V["rep"] > 1:
                 self._emu_mod = n_g
-            where = None
+            where = dict(layout="picks", gcand=gcand)
         elif isinstance(d_out, str) and d_out == "topk":     # the top regions of the ranking (this rank's own): sel = arange
             where = dict(layout=1, buf=unl, max_select=int(unl.shape[0]) - 8)
             res = unl.to_host(self.sel_stream)
@@ -818,14 +820,40 @@ class HotPath:
         if getattr(self, "_emu_mod", 0):                    # (SSDR_EMULATE_WORLD: the picks index the repeated rows)
             sel = sel % self._emu_mod
         si = np.asarray(sel, np.int64)
-        if where == "host" and getattr(self, "_last_comm", None) is not None:
-            where = None             # (a sharded round: sel indexes all ranks' candidates, unl is this rank's share; label_selected refuses it anyway)
-        if where == "host":          # decided on the host: the picks as global region ids (label_selected uploads them)
+        if getattr(self, "_last_comm", None) is not None:
+            where = self._sharded_where(where, si, unl, self._last_comm)
+        elif where == "host":        # decided on the host: the picks as global region ids (label_selected uploads them)
             ids = unl.b if isinstance(unl, _Pairs) else np.asarray([u[1] for u in unl], np.int64)
             where = dict(layout=None, items=np.asarray(ids, np.int64).reshape(-1)[si])
-        self._last_sel = where      # where the picks of this selection lie, for label_selected (None: a sharded round)
+        self._last_sel = where      # where the picks of this selection lie, for label_selected
         self._selected = _Pairs(np.asarray(self.unl_cloud_ids)[si], np.asarray(self.unl_sp)[si])      # (room id, superpoint in room)
         return sel, unl
+
+    def _sharded_where(self, where, si, unl, comm):
+        """Where a sharded selection's picks lie, for label_selected(comm=).  fps / k-center: the picks and the global candidate list are replicated; a rank's
+        items are the picks whose region it holds (`own`: their positions among all picks, which is also their place in self.selected).  edcd / topk: a
+        rank holds its own picks only.  Host rule: the items and their 64-bit walk keys (cloud key << 32 | position in pick order) are made here."""
+        D = self.global_order if self.global_order is not None else self._dist
+        Smax, rank = D["Smax"], comm.rank
+        if int(os.environ.get("SSDR_EMULATE_WORLD", "0")) > 1:
+            return dict(refuse="the selection ran under SSDR_EMULATE_WORLD (repeated rows: only its timing means anything)")
+        if isinstance(where, dict) and where["layout"] == "picks":          # device rule, fps / k-center
+            return dict(where, own=np.flatnonzero(where["gcand"][si] // Smax == rank))
+        if isinstance(where, dict):                                         # device rule, edcd / topk: the chain's own result buffer
+            return dict(where, own=np.arange(len(si)))
+        if self.selector in ("fps", "kcenter"):
+            gid = np.asarray(self._gcand_h, np.int64)[si]
+            gc = D["gcloud"][gid]
+            first = np.full(comm.world * D["Bmax"], 1 << 30, np.int64)
+            np.minimum.at(first, gc, np.arange(len(gid)))                  # a cloud's first appearance among ALL picks
+            own = np.flatnonzero(gid // Smax == rank)
+            return dict(layout=None, items=gid[own] - rank * Smax, keys=(first[gc[own]] << 32) | own, own=own)
+        ids = np.asarray(unl.b if isinstance(unl, _Pairs) else [u[1] for u in unl], np.int64).reshape(-1)[si]
+        order = np.asarray(self._gorder_h, np.int64)                       # a cloud's first place in the global ranking among the regions that compete
+        r = np.flatnonzero(D["valid"][order])
+        key = np.full(comm.world * D["Bmax"], 0x7f7f7f7f, np.int64)
+        np.minimum.at(key, D["gcloud"][order[r]], r)
+        return dict(layout=None, items=ids, keys=(key[D["gcloud"][rank * Smax + ids]] << 32) | np.arange(len(ids)), own=np.arange(len(ids)))
 
     def gcn_rows(self, info_only=False):
         """what the last "coregcn" selection left on the device: (evaluation rows [rows,129] float64, trained parameters, (loss at step 0, loss after the
@@ -860,15 +888,23 @@ class HotPath:
         self.pseudo_mask, self.pseudo_label = DevArray.from_host(np.ascontiguousarray(a[0])), DevArray.from_host(np.ascontiguousarray(a[1]))
         return self
 
-    def label_selected(self, mode="NAIL", threshold=0.9, min_size=None, budget=None):
+    def label_selected(self, mode="NAIL", threshold=0.9, min_size=None, budget=None, comm=None):
         """_help() / oracle_labeling() for every cloud that received picks (sampler2.py:124-216, called from sampling() :676-684, :775-781, :796-806), on
         the device and from the device buffers of the last selection: the picks become pseudo labels while the click budget (default: the round's
         batch_size, as sampling() sets it) lasts.  Afterwards self.labeled, the skip mask and selected_class_list are what set_labeled() would
-        produce for the next round: step_selection() can be called again.  Returns a LabelResult."""
+        produce for the next round: step_selection() can be called again.  Returns a LabelResult.
+        comm: the communicator of the last selection (a sharded round): every rank judges its own picks, the verdict records are all-gathered on the
+        selection stream, every rank runs the same walk over all of them and applies its own.  The counters, budget_left and the class list are then
+        global and equal on all ranks; `used` / `walk_pos` are this rank's used picks and their positions in the global walk."""
         from . import sampler
-        if getattr(self, "_last_comm", None) is not None:
-            raise ValueError("label_selected: the last selection ran with a communicator; the budget walk is global over all ranks' picks and a sharded "
-                             "labelling is not offered")
+        last = getattr(self, "_last_comm", None)
+        if last is not None and comm is None:
+            raise ValueError("label_selected: the last selection ran with a communicator; the budget walk is global over all ranks' picks: pass that "
+                             "communicator (label_selected(comm=comm))")
+        if comm is not None:
+            if comm is not last:
+                raise ValueError("label_selected: comm must be the communicator of the last selection")
+            return self._label_selected_sharded(comm, mode, threshold, min_size, budget)
         where = getattr(self, "_last_sel", None)
         if where is None:
             raise RuntimeError("label_selected: no selection to label (run step_selection() / step() first)")
@@ -917,7 +953,79 @@ class HotPath:
         self.set_labeled({b: set(np.flatnonzero(mask & (self.sp_cloud_h == b)).tolist()) for b in range(self.B)})
         self._last_sel = None                                # (these picks are spent)
         return LabelResult(self, dict(zip(sampler.LABEL_COUNTERS, (int(x) for x in out[:6]))), int(out[7]), used, entries,
-                           dict(wave=int(out[10]), block=int(out[11])))
+                           dict(wave=int(out[10]), block=int(out[11])), np.flatnonzero(used_f[proc] != 0))
+
+    def _label_selected_sharded(self, comm, mode, threshold, min_size, budget):
+        """label_selected over a sharded round: walk keys -> verdict half -> all-gather of the records (the fourth exchange) -> walk half"""
+        from . import sampler
+        where = getattr(self, "_last_sel", None)
+        if where is None:
+            raise RuntimeError("label_selected: no selection to label (run step_selection(comm) / step(comm) first)")
+        if where.get("refuse"):
+            raise ValueError("label_selected: " + where["refuse"])
+        L, st, T = _lib.lib(), self.sel_stream, self._sel_static
+        D = self._dist_setup(comm); V = D["dev"]
+        W, rank, Smax, Bmax = comm.world, comm.rank, D["Smax"], D["Bmax"]
+        m = sampler.label_mode([mode] if isinstance(mode, str) else mode)
+        batch = int(D["batch"])                               # the round's batch_size is one number for all ranks
+        budget = batch if budget is None else int(budget)
+        min_size = self.min_size if min_size is None else int(min_size)
+        if self.pseudo_mask is None:
+            self.set_pseudo_gt(np.zeros((2, self.n_pts), np.float32))
+        # the record slots per rank: the most picks any rank can hold, from what _dist_setup exchanged
+        # (fps / kcenter: the replicated chain may hand ALL picks to one rank, and the all-gather needs the same slot count on every rank)
+        M = {"edcd": min(batch, int(D["nvalid_all"].max())), "topk": min(batch, Smax)}.get(self.selector, V["picks"])
+        M = max(int(M), 1)
+        d_items, d_n, d_keys = DevArray((M,), np.int32), DevArray((1,), np.int32), DevArray((M,), np.uint64)
+        if where["layout"] is None:                           # host rule: items and keys were made on the host
+            k = len(where["items"])
+            assert k <= M
+            _lib.check(L.ssdr_memcpy_h2d_on(d_items.ptr, _lib.ptr(np.ascontiguousarray(where["items"], np.int32)), 4 * k, st))
+            _lib.check(L.ssdr_memcpy_h2d_on(d_keys.ptr, _lib.ptr(np.ascontiguousarray(where["keys"]).astype(np.uint64)), 8 * k, st))
+            _lib.check(L.ssdr_memcpy_h2d_on(d_n.ptr, _lib.ptr(np.array([k], np.int32)), 4, st))
+        elif where["layout"] == "picks":                      # the replicated picks over the replicated global candidate list
+            off = 16 + W + W * V["nu_max"]
+            _lib.check(L.ssdr_oracle_label_keys_dev(V["d_out"].ptr, V["picks"], V["d_plan"].ptr + 4 * 8, V["d_plan"].ptr + 4 * off, W * V["nu_max"], D["d_gcloud"].ptr, Smax,
+                                                    W * Bmax, rank, W, None, d_items.ptr, d_n.ptr, M, d_keys.ptr, st))
+        else:                                                 # the rank's own picks; a cloud's key is its first place in the global ranking
+            d_key = DevArray((W * Bmax,), np.int32)
+            ms = min(int(where["max_select"]), M)
+            _lib.check(L.ssdr_oracle_label_items_dev(where["buf"].ptr, where["layout"], int(where["max_select"]), D["d_ord"].ptr, W * Smax, V["d_glab"].ptr, D["d_gcloud"].ptr,
+                                                     W * Bmax, d_items.ptr, ms, d_n.ptr, d_key.ptr, st))
+            _lib.check(L.ssdr_oracle_label_keys_dev(None, 0, None, None, 0, D["d_gcloud"].ptr, Smax, W * Bmax, rank, W, d_key.ptr, d_items.ptr, d_n.ptr, M, d_keys.ptr, st))
+        nc = int(self.cfg.num_classes)
+        max_region = int(self.sp_size_h.max()) if self.S else 1
+        d_send, d_gath = DevArray((M * _lib.LABEL_RECORD_BYTES,), np.uint8), DevArray((W, M * _lib.LABEL_RECORD_BYTES), np.uint8)
+        _lib.check(L.ssdr_oracle_label_verdict_dev(self.tile_l.ptr, self.cls.ptr, self.n_pts, self.sp_off.ptr, self.sp_pts.ptr, self.S, d_items.ptr, d_n.ptr, M, d_keys.ptr,
+                                                   max_region, max(nc, 1), nc, m, float(threshold), min_size, d_send.ptr, st))
+        comm.allgather_(d_send, d_gath, st)                  # exchange 4: every rank's verdict records
+        cap = max(1, min(W * M * nc, max(budget, 0) + nc + 1))
+        d_budget = DevArray.from_host(np.array([budget], np.int64), st)
+        d_used, d_pos = DevArray((M,), np.uint8), DevArray((M,), np.int32)
+        d_labeled = DevArray.from_host(self.labeled_mask.astype(np.uint8) if self.S else np.zeros(1, np.uint8), st)
+        d_cls, d_out = DevArray((cap,), np.int32), DevArray((12,), np.int64)
+        _lib.check(L.ssdr_oracle_label_walk_dev(d_gath.ptr, rank, W, self.cls.ptr, self.n_pts, self.sp_off.ptr, self.sp_pts.ptr, self.S, d_items.ptr, d_n.ptr, M, max_region,
+                                                nc, d_budget.ptr, self.pseudo_mask.ptr, self.pseudo_label.ptr, d_used.ptr, d_labeled.ptr, d_cls.ptr, cap, d_pos.ptr,
+                                                d_out.ptr, st))
+        out = d_out.to_host(st)                              # waits for the selection stream alone
+        sampler.label_status_check(int(out[8]))
+        n_items = int(d_n.to_host(st)[0])
+        used_f, pos = d_used.to_host(st)[:n_items], d_pos.to_host(st)[:n_items]
+        own = np.asarray(where["own"], np.int64)
+        if len(own) != n_items:
+            raise RuntimeError("label_selected: the device found %d picks of this rank, the selection read back %d" % (n_items, len(own)))
+        slots = np.flatnonzero(used_f != 0)
+        slots = slots[np.argsort(pos[slots], kind="stable")]      # this rank's used picks in the order the global walk met them
+        sel_pairs = self.__dict__.get("_selected")
+        used = _Pairs(np.asarray(sel_pairs.a)[own[slots]], np.asarray(sel_pairs.b)[own[slots]])
+        entries = d_cls.to_host(st)[: int(out[6])]
+        self._class_list_h = np.concatenate([self._class_list_h, entries]).astype(np.int32)      # the global list, identical on every rank
+        self.selected_class_list = DevArray.from_host(self._class_list_h)
+        mask = d_labeled.to_host(st)[: self.S] != 0
+        self.set_labeled({b: set(np.flatnonzero(mask & (self.sp_cloud_h == b)).tolist()) for b in range(self.B)})      # (drops _dist: the next round redoes the global draw)
+        self._last_sel = None
+        return LabelResult(self, dict(zip(sampler.LABEL_COUNTERS, (int(x) for x in out[:6]))), int(out[7]), used, entries,
+                           dict(wave=int(out[10]), block=int(out[11])), pos[slots].astype(np.int64))
 
     def step(self, comm=None, timed_stages=False):
         """One pass of the hot path over the loaded batch of rooms.  Returns the selected candidate indices."""
@@ -939,10 +1047,13 @@ class HotPath:
 class LabelResult:
     """What HotPath.label_selected / ALRound.label hand back: `mask` / `label` (device, float32 [n]: the two rows of pseudo_gt over all points, the
     HotPath's own resident arrays), `used` as (room id, superpoint in room) pairs in the order the walk met them, the six `counters` of the
-    reference's `w`, `budget_left` (may be negative), `class_entries` appended to selected_class_list, `forms`: regions judged per kernel form."""
-    def __init__(self, hp, counters, budget_left, used, class_entries, forms):
+    reference's `w`, `budget_left` (may be negative), `class_entries` appended to selected_class_list, `forms`: regions judged per kernel form,
+    `walk_pos`: the position of every entry of `used` in the walk.  After a sharded labelling the counters, budget_left, class_entries and forms are
+    global (equal on all ranks), `used` / `walk_pos` this rank's share of the global walk."""
+    def __init__(self, hp, counters, budget_left, used, class_entries, forms, walk_pos=None):
         self._hp, self.mask, self.label = hp, hp.pseudo_mask, hp.pseudo_label
         self.counters, self.budget_left, self._used, self.class_entries, self.forms = counters, budget_left, used, class_entries, forms
+        self.walk_pos = walk_pos
 
     @property
     def used(self):
@@ -983,13 +1094,24 @@ class ALRound:
     round as the reference runs it: `n_batches` batches of len(rooms) tiles go through front end -> KNN pyramid -> inference (three streams, three
     buffer sets, batches overlapped), their tiles / labels / probabilities / features land in the round's arrays, then scoring over all points and
     the one-call device chain (ssdr_gcn_fps_sampling_dev) over all clouds' regions.  Tiles of batch b are cut from the same raw rooms with the
-    randomness of room id b * len(rooms) + i (another pick point, shuffle and padding draw: another tile)."""
+    randomness of room id b * len(rooms) + i (another pick point, shuffle and padding draw: another tile).
+    comm: a sharded round.  A rank owns a contiguous share of the batches (np.array_split over the ranks; uneven shares are allowed, a rank without a
+    batch is refused), allocates and infers only those, and keeps their GLOBAL tile ids for the randomness, the labelled stand-in and room_ids: the union
+    of the ranks' tiles is the single-process round's.  run() and label() then pass the communicator on to the scoring, the selection and the oracle."""
     SLOTS = 4          # batches in flight = HIP streams = the runtime's hardware queues (2: 54.9 ms for 17 batches, 3: 52.2, 4: 49.1, 5: 56.9, 6: 49.4, 8: 49.6; a stream per STAGE: 60-64)
 
     def __init__(self, weights, rooms, n_batches, config=ConfigS3DIS, batch_size=10000, round_num=5, labeled_per_tile=15, precision="f32",
-                 selector="fps", tiles32=True, seed=0, gcn_number=1, gcn_top=0, min_size=1, gcn_steps=20000, gcn_dropout=0.3, gcn_seed=0, gcn_form="auto"):
+                 selector="fps", tiles32=True, seed=0, gcn_number=1, gcn_top=0, min_size=1, gcn_steps=20000, gcn_dropout=0.3, gcn_seed=0, gcn_form="auto", comm=None):
         L = _lib.lib()
-        self.cfg, self.nb, self.B, self.rooms = config, int(n_batches), len(rooms), rooms
+        self.comm = comm
+        self.batch_ids = list(range(int(n_batches)))          # the global ids of this process's batches
+        if comm is not None:
+            if selector == "coregcn":
+                raise ValueError('selector="coregcn" with a communicator: the sharded form of the trained-GCN selector is not offered')
+            if comm.world > int(n_batches):                   # (raised on every rank: nobody is left waiting in an exchange)
+                raise ValueError("ALRound: %d batches cannot be shared among %d ranks (a rank would own none)" % (int(n_batches), comm.world))
+            self.batch_ids = [int(b) for b in np.array_split(np.arange(int(n_batches)), comm.world)[comm.rank]]
+        self.cfg, self.nb, self.B, self.rooms = config, len(self.batch_ids), len(rooms), rooms
         N = config.num_points
         self.tiles = self.nb * self.B
         # five streams: front end and pyramid alternate between two streams each by the parity of the batch, so that a cross-stream wait ("everything
@@ -1024,7 +1146,7 @@ class ALRound:
         self.batches = []
         h0 = self.work[0]
         for b in range(self.nb):
-            draws = [h0.draw_room(r[0], b * self.B + i) for i, r in enumerate(rooms)]
+            draws = [h0.draw_room(r[0], self.batch_ids[b] * self.B + i) for i, r in enumerate(rooms)]
             lo, hi = b * self.B * N, (b + 1) * self.B * N
             self.batches.append(dict(centers=np.ascontiguousarray(np.stack([d["center"] for d in draws]), np.float32),
                                      perm=DevArray.from_host(np.stack([d["perm"] for d in draws])), dup=DevArray.from_host(np.stack([d["dup"] for d in draws])),
@@ -1037,16 +1159,17 @@ class ALRound:
         from .synthetic import superpoints_from_tile
         tiles = self.xyz.to_host().reshape(self.tiles, N, 3)
         offs, pts, cloud, labeled = [np.zeros(1, np.int64)], [], [], {}
+        tile_ids = [bg * self.B + i for bg in self.batch_ids for i in range(self.B)]      # global tile ids (a sharded round: this rank's)
         for t in range(self.tiles):
             o, p = superpoints_from_tile(tiles[t])
             base = int(sum(len(x) for x in cloud))
             pts.append(p.astype(np.int64) + t * N); offs.append(o[1:].astype(np.int64) + offs[-1][-1]); cloud.append(np.full(len(o) - 1, t, np.int32))
-            rng = np.random.default_rng([seed, t, 1])
+            rng = np.random.default_rng([seed, tile_ids[t], 1])
             n_sp = len(o) - 1
             labeled[t] = set((base + rng.choice(n_sp, min(labeled_per_tile, n_sp), replace=False)).tolist())
         sel_list = np.random.default_rng([seed, 999983]).integers(0, config.num_classes, 4000)
         self.sel = HotPath.from_device(self.xyz, self.probs, self.f32, self.tile_l, np.concatenate(offs), np.concatenate(pts), np.concatenate(cloud), labeled, sel_list,
-                                       config, batch_size=batch_size, round_num=round_num, selector=selector, gcn_number=gcn_number, gcn_top=gcn_top, min_size=min_size, seed=seed,
+                                       config, room_ids=tile_ids, batch_size=batch_size, round_num=round_num, selector=selector, gcn_number=gcn_number, gcn_top=gcn_top, min_size=min_size, seed=seed,
                                        gcn_steps=gcn_steps, gcn_dropout=gcn_dropout, gcn_seed=gcn_seed, gcn_form=gcn_form)
         self.sel.stream = self.sel.score_stream = self.sel.sel_stream = s_i
         self.sel.front_stream = s_i; self.sel.pipelined = True
@@ -1099,8 +1222,8 @@ class ALRound:
     def run(self):
         """the whole round; returns (picked candidate indices, candidate list) as HotPath.step does"""
         self.infer_all()
-        self.sel._score_async(None)
-        self.sel._select_issue(None)
+        self.sel._score_async(self.comm)
+        self.sel._select_issue(self.comm)
         out = self.sel._select_collect()
         from . import knn as _knn
         for st in [self.s_knn] + self.bstreams:
@@ -1112,7 +1235,7 @@ class ALRound:
     def label(self, mode="NAIL", threshold=0.9, min_size=None, budget=None):
         """the oracle over the round's picks (HotPath.label_selected on the round's arrays): the labelled set, the class list and the pseudo labels
         are then those of the next round"""
-        return self.sel.label_selected(mode=mode, threshold=threshold, min_size=min_size, budget=budget)
+        return self.sel.label_selected(mode=mode, threshold=threshold, min_size=min_size, budget=budget, comm=self.comm)
 
 
 class BatchStreams:
