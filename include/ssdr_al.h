@@ -595,6 +595,31 @@ int ssdr_vote_smooth_dev(float* d_test_probs, const int32_t* d_point_idx, const 
 int ssdr_confusion_dev(const float* d_probs, int num_classes, const int32_t* d_proj_idx, const int32_t* d_labels, size_t n, int32_t* d_pred,
                        uint64_t* d_confusion, double* d_iou, void* stream);
 
+/* ---- test-time generator chain (S3/s3dis_dataset_test.py:85-151, get_batch; csrc/vote.hip) ---------------------------
+ * State, owned by the caller, over ALL evaluation clouds concatenated (cloud c = rows [cloud_offsets[c], cloud_offsets[c+1]), host int64
+ * [num_clouds + 1], cloud_offsets[0] = 0): d_points f32 [n,3], d_colors f32 [n,color_dim], d_labels i32 [n] (optional), d_possibility f64 [n],
+ * d_cloud_min f64 [num_clouds] (min_possibility) and d_cloud_arg i32 [num_clouds] (the LOCAL row of each cloud's first minimum).
+ * ssdr_vote_init_dev: every cloud's minimum and first arg-min of the map as it stands (init_possibility, :85-92).
+ * ssdr_vote_tiles_dev: num_tiles tiles of get_batch's generator loop (:104-147), in order, tile t + 1 reading what tile t left: the cloud
+ *   = first arg-min of d_cloud_min, the centre = its arg-min point + d_noise[t] (float32), the tile = what ssdr_tile_select_possibility_dev
+ *   gives for that cloud, centre, d_perm[t] and d_dup_u[t] (d_noise f32 [num_tiles,3], d_perm i32 [num_tiles,num_points], d_dup_u f32
+ *   [num_tiles,num_points]), then the possibility update and the cloud's new minimum / arg-min.  Outputs: d_out_xyz [num_tiles,num_points,3],
+ *   d_out_feat [num_tiles,num_points,3+color_dim] (optional), d_out_idx [num_tiles,num_points] = GLOBAL rows (cloud_offsets[c] + queried_idx),
+ *   d_out_labels [num_tiles,num_points] (optional; needs d_labels), d_out_cloud i32 [num_tiles], d_out_center f32 [num_tiles,3].
+ *   Enqueue only: no device value is read by the host, and a call does not wait for the stream (the offset table is uploaded only when it
+ *   differs from the last call's on that stream).  The map comes out bit for bit the same on every run.
+ * Refused before anything is launched: no clouds, an empty cloud, num_tiles or num_points 0, d_out_labels without d_labels
+ * (SSDR_ERR_INVALID); more than 4096 clouds, more than 0x3fffffff points or tile rows in all (SSDR_ERR_UNSUPPORTED).
+ * ssdr_vote_tile_launches: kernel launches ssdr_vote_tiles_dev makes per tile (plus one per call). */
+int ssdr_vote_init_dev(const double* d_possibility, const int64_t* cloud_offsets, size_t num_clouds, double* d_cloud_min, int32_t* d_cloud_arg,
+                       void* stream);
+int ssdr_vote_tiles_dev(const float* d_points, const float* d_colors, int color_dim, const int32_t* d_labels, double* d_possibility,
+                        double* d_cloud_min, int32_t* d_cloud_arg, const int64_t* cloud_offsets, size_t num_clouds,
+                        size_t num_tiles, size_t num_points, const float* d_noise, const int32_t* d_perm, const float* d_dup_u, float color_scale,
+                        float* d_out_xyz, float* d_out_feat, int32_t* d_out_idx, int32_t* d_out_labels, int32_t* d_out_cloud, float* d_out_center,
+                        void* stream);
+int ssdr_vote_tile_launches(void);
+
 /* ---- plain device memory for callers without their own allocator (tests, the ctypes mirror) ---------- */
 int ssdr_dev_alloc(size_t bytes, void** d_ptr);
 int ssdr_dev_free(void* d_ptr);

@@ -133,6 +133,8 @@ def lib():
         L.ssdr_chamfer3d_forward_dev.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]
         L.ssdr_vote_smooth_dev.argtypes = [vp, vp, vp, sz, i32, f64, vp, vp]
         L.ssdr_confusion_dev.argtypes = [vp, i32, vp, vp, sz, vp, vp, vp, vp]
+        L.ssdr_vote_init_dev.argtypes = [vp, vp, sz, vp, vp, vp]
+        L.ssdr_vote_tiles_dev.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp]
         L.ssdr_main_stream.argtypes = [C.POINTER(vp)]
         L.ssdr_mask_regions_dev.argtypes = [vp, vp, sz, sz, vp, vp]
         L.ssdr_gather_rows_dev.argtypes = [vp, vp, sz, sz, vp, vp]

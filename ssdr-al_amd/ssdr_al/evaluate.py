@@ -1,5 +1,8 @@
 """Mirror of the evaluation tail of the reference ("next" row N2): vote smoothing, re-projection, confusion, IoU
-(/root/reference/SSDR_AL_s3dis/RandLANet.py:326-334, 353-411; helper_tool.py:237-262; utils/data_prepare_s3dis.py:69)."""
+(/root/reference/SSDR_AL_s3dis/RandLANet.py:326-334, 353-411; helper_tool.py:237-262; utils/data_prepare_s3dis.py:69), and the
+test-time voting loop that composes them with the generator chain (VoteTester: RandLANet.py:290-424, s3dis_dataset_test.py:85-151)."""
+import ctypes as C
+
 import numpy as np
 
 from . import _lib
@@ -52,3 +55,271 @@ def IoU_from_confusions(confusions):
     _lib.check(_lib.lib().ssdr_confusion_dev(d_p.ptr, C, None, d_dummy.ptr, 0, None, d_conf.ptr, d_iou.ptr, None))
     _lib.sync()
     return d_iou.to_host()
+
+
+def _iou_host(confusions):
+    """helper_tool.py:237-262 on a host matrix of any dtype (the rescaled float32 sub-cloud confusion of RandLANet.py:362-368)."""
+    c = np.asarray(confusions)
+    tp = np.diagonal(c, axis1=-2, axis2=-1)
+    tp_fn = np.sum(c, axis=-1)
+    tp_fp = np.sum(c, axis=-2)
+    iou = tp / (tp_fp + tp_fn - tp + 1e-6)
+    mask = tp_fn < 1e-3
+    counts = np.sum(1 - mask, axis=-1, keepdims=True)
+    miou = np.sum(iou, axis=-1, keepdims=True) / (counts + 1e-6)
+    iou += mask * miou
+    return iou
+
+
+class VoteTester:
+    """Network.evaluate_test_s3dis (RandLANet.py:290-424) over the test-time generator (s3dis_dataset_test.py:85-151), device-resident.
+
+    ``clouds[c]`` = dict(xyz [n,3], rgb [n,3], labels [n] or None, proj_idx=None, raw_labels=None): the sub-sampled cloud, and
+    optionally the raw cloud's nearest sub-point per raw point with the raw labels (val_proj / val_labels); without them the
+    "full cloud" is the sub-cloud itself.  All clouds live concatenated on the device together with the possibility map, the
+    per-cloud minima and test_probs.  The host draws the randomness (initial map from (seed, cloud), noise / shuffle / padding
+    draws from (seed, epoch, step)), reads the cloud minima once per epoch and the final matrices, nothing else.
+
+    The generator chain (ssdr_vote_tiles_dev) runs on a stream of its own, DEPTH batches ahead of the network at most (the tile
+    and draw buffers exist DEPTH times); the draws are uploaded on a third stream, so the host waits for the generator of DEPTH
+    batches ago only, never for the network."""
+
+    DEPTH = 2
+
+    def __init__(self, weights, clouds, config=None, precision="f32", seed=0, num_votes=100, test_smooth=0.95, possibility=None):
+        from . import randlanet
+        from .helper_tool import ConfigS3DIS
+        cfg = self.cfg = ConfigS3DIS if config is None else config
+        L = _lib.lib()
+        _lib.check(L.ssdr_init(0))
+        self.seed, self.num_votes, self.test_smooth = int(seed), num_votes, float(test_smooth)
+        self.N, self.B, self.steps, self.C = int(cfg.num_points), int(cfg.val_batch_size), int(getattr(cfg, "val_steps", 100)), int(cfg.num_classes)
+        self.nc = len(clouds)
+        sizes = [len(c["xyz"]) for c in clouds]
+        self.off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        self.n = int(self.off[-1])
+        self.has_labels = self.nc > 0 and all(c.get("labels") is not None for c in clouds)
+        if possibility is None:
+            possibility = [np.random.default_rng([self.seed, c]).random(n) * 1e-3 for c, n in enumerate(sizes)]      # init_possibility, test.py:85-92
+        poss = np.concatenate([np.asarray(p, np.float64) for p in possibility]) if self.nc else np.zeros(0)
+        cat = lambda key, dt, w: (np.concatenate([np.asarray(c[key], dt).reshape(len(c["xyz"]), *w) for c in clouds]) if self.nc else np.zeros((0, *w), dt))
+        self.d_points = DevArray.from_host(cat("xyz", np.float32, (3,)))
+        self.d_colors = DevArray.from_host(cat("rgb", np.float32, (3,)))
+        self.d_labels = DevArray.from_host(cat("labels", np.int32, ())) if self.has_labels else None
+        self.d_poss = DevArray.from_host(poss)
+        self.d_cloud_min, self.d_cloud_arg = DevArray((max(self.nc, 1),), np.float64), DevArray((max(self.nc, 1),), np.int32)
+        # the raw clouds: global rows of their nearest sub-points, their labels (val_proj, val_labels)
+        proj, raw_lab, self.raw_off = [], [], [0]
+        for c, cl in enumerate(clouds):
+            pi = cl.get("proj_idx")
+            proj.append(self.off[c] + (np.arange(sizes[c]) if pi is None else np.asarray(pi, np.int64)))
+            rl = cl.get("raw_labels") if pi is not None else cl.get("labels")
+            raw_lab.append(None if rl is None else np.asarray(rl, np.int32))
+            self.raw_off.append(self.raw_off[-1] + len(proj[-1]))
+        self.n_raw = self.raw_off[-1]
+        self.d_proj = DevArray.from_host(np.concatenate(proj).astype(np.int32)) if self.nc else None
+        self.has_raw_labels = self.nc > 0 and all(r is not None and len(r) == len(p) for r, p in zip(raw_lab, proj))
+        self._raw_labels = np.concatenate(raw_lab) if self.has_raw_labels else None
+        self.test_probs = DevArray.from_host(np.zeros((self.n, self.C), np.float32))
+        self.owner = DevArray.from_host(np.full(max(self.n, 1), -1, np.int32))
+        self.net = randlanet.Network(cfg).load(weights).set_precision(precision)
+        mk = lambda: (lambda p: (_lib.check(L.ssdr_stream_create(C.byref(p))), p.value)[1])(C.c_void_p())
+        self.s_gen, self.s_up, self.s_net = mk(), mk(), mk()
+        ev = lambda: (lambda p: (_lib.check(L.ssdr_event_create(C.byref(p))), p.value)[1])(C.c_void_p())
+        N, B, K = self.N, self.B, cfg.k_n
+        self.pads = bool(sizes) and min(sizes) < N            # the padding draws matter only when a cloud is smaller than a tile
+        self.sets = []
+        for _ in range(self.DEPTH):
+            self.sets.append(dict(
+                noise=DevArray((B, 3), np.float32), perm=DevArray((B, N), np.int32), dup=DevArray.from_host(np.zeros((B, N), np.float32)),
+                xyz=DevArray((B, N, 3), np.float32), feat=DevArray((B, N, 6), np.float32), idx=DevArray((B, N), np.int32),
+                labels=DevArray((B, N), np.int32) if self.has_labels else None, cloud=DevArray((B,), np.int32), center=DevArray((B, 3), np.float32),
+                ready=ev(), consumed=ev(), gen_used=False, net_used=False))
+        lv = [N]
+        for r in cfg.sub_sampling_ratio:
+            lv.append(lv[-1] // r)
+        self.neigh = [DevArray((B, lv[i], K), np.int32) for i in range(cfg.num_layers)]
+        self.interp = [DevArray((B, lv[i], 1), np.int32) for i in range(cfg.num_layers)]
+        self.probs, self.f32 = DevArray((B * N, self.C), np.float32), DevArray((B * N, 32), np.float32)
+        self.epochs, self.tiles, self.min_history = 0, 0, []
+        self.confusion = self.ious = self.sub_confusion = self.sub_ious = None
+        self._issued = self._done = 0            # batches whose generator / network has been enqueued
+        self._step_in_epoch = 0
+        if self.nc:
+            _lib.check(L.ssdr_vote_init_dev(self.d_poss.ptr, _lib.ptr(self.off), self.nc, self.d_cloud_min.ptr, self.d_cloud_arg.ptr, self.s_gen))
+
+    def close(self):
+        L = _lib.lib()
+        for s in (getattr(self, "s_gen", None), getattr(self, "s_up", None), getattr(self, "s_net", None)):
+            if s:
+                L.ssdr_stream_sync(s)
+        for st in getattr(self, "sets", []):
+            L.ssdr_event_destroy(st["ready"]); L.ssdr_event_destroy(st["consumed"])
+        for s in ("s_gen", "s_up", "s_net"):
+            if getattr(self, s, None):
+                L.ssdr_stream_destroy(getattr(self, s)); setattr(self, s, None)
+        self.sets = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- randomness (host, as everywhere) -------------------------------------------------------------------------------
+    def draw(self, epoch, step):
+        """the draws of one batch from (seed, epoch, step): noise [B,3] = normal(0, noise_init / 10) cast to float32 (test.py:114-115), one shuffle
+        permutation per tile (DP.shuffle_idx, :125), the padding draws of data_aug (:137-141; zeros when no cloud is smaller than a tile)"""
+        rng = np.random.default_rng([self.seed, int(epoch), int(step)])
+        noise = rng.normal(scale=self.cfg.noise_init / 10, size=(self.B, 3)).astype(np.float32)
+        perm = np.stack([rng.permutation(self.N) for _ in range(self.B)]).astype(np.int32)
+        dup = rng.random((self.B, self.N), dtype=np.float32) if self.pads else None
+        return dict(noise=noise, perm=perm, dup=dup)
+
+    # ---- the two halves of a batch, both enqueue-only ---------------------------------------------------------------------
+    def _generate(self, draws):
+        """get_batch (test.py:97-151) of the next batch on the generator's stream, into buffer set (batch % DEPTH)"""
+        if self.nc == 0:
+            raise ValueError("VoteTester: no clouds")
+        L = _lib.lib()
+        st = self.sets[self._issued % self.DEPTH]
+        if st["gen_used"]:
+            _lib.check(L.ssdr_stream_wait_event(self.s_up, st["ready"]))       # the draws of DEPTH batches ago have been read
+        ups = [("noise", np.float32), ("perm", np.int32)] + ([("dup", np.float32)] if draws.get("dup") is not None else [])
+        for k, dt in ups:
+            a = np.ascontiguousarray(draws[k], dt)
+            assert a.shape == st[k].shape, (k, a.shape, st[k].shape)
+            _lib.check(L.ssdr_memcpy_h2d_on(st[k].ptr, _lib.ptr(a), a.nbytes, self.s_up))      # waits for the upload stream alone
+        if st["net_used"]:
+            _lib.check(L.ssdr_stream_wait_event(self.s_gen, st["consumed"]))   # the tile buffers' last reader
+        _lib.check(L.ssdr_vote_tiles_dev(self.d_points.ptr, self.d_colors.ptr, 3, self.d_labels.ptr if self.has_labels else None, self.d_poss.ptr,
+                                         self.d_cloud_min.ptr, self.d_cloud_arg.ptr, _lib.ptr(self.off), self.nc, self.B, self.N,
+                                         st["noise"].ptr, st["perm"].ptr, st["dup"].ptr, 1.0 / 255.0, st["xyz"].ptr, st["feat"].ptr, st["idx"].ptr,
+                                         st["labels"].ptr if self.has_labels else None, st["cloud"].ptr, st["center"].ptr, self.s_gen))
+        _lib.check(L.ssdr_event_record(st["ready"], self.s_gen))
+        st["gen_used"] = True
+        self._issued += 1
+        return st
+
+    def _network(self):
+        """pyramid, network and votes (RandLANet.py:319-334) of the oldest generated batch, on the network's stream"""
+        L = _lib.lib()
+        cfg, B, N = self.cfg, self.B, self.N
+        st = self.sets[self._done % self.DEPTH]
+        s = self.s_net
+        _lib.check(L.ssdr_stream_wait_event(s, st["ready"]))
+        arr = C.c_void_p * cfg.num_layers
+        r = np.asarray(cfg.sub_sampling_ratio, np.int32)
+        _lib.check(L.ssdr_knn_pyramid_dev(st["xyz"].ptr, B, N, cfg.num_layers, _lib.ptr(r), cfg.k_n, arr(*[a.ptr for a in self.neigh]), None,
+                                          arr(*[a.ptr for a in self.interp]), s))
+        self.net.infer_dev(B, N, st["feat"].ptr, st["xyz"].ptr, [a.ptr for a in self.neigh], [a.ptr for a in self.interp], self.probs.ptr, self.f32.ptr, s)
+        # tile by tile, in batch order: a point in two tiles of the batch is smoothed twice (:330-334)
+        for j in range(B):
+            _lib.check(L.ssdr_vote_smooth_dev(self.test_probs.ptr, st["idx"].ptr + 4 * j * N, self.probs.ptr + 4 * j * N * self.C, N, self.C,
+                                              self.test_smooth, self.owner.ptr, s))
+        _lib.check(L.ssdr_event_record(st["consumed"], s))
+        st["net_used"] = True
+        self._done += 1
+        self.tiles += B
+        return st
+
+    def _drain(self):
+        while self._done < self._issued:
+            self._network()
+
+    def run_batch(self, draws=None):
+        """One get_batch + network + votes, finished on return.  Returns the batch's device arrays (xyz, feat, idx, labels, cloud, center,
+        probs): they are overwritten by the batch after the next."""
+        self._drain()
+        if draws is None:
+            draws = self.draw(self.epochs, self._step_in_epoch)
+        self._generate(draws)
+        st = self._network()
+        self._step_in_epoch += 1
+        _lib.sync(self.s_gen)
+        _lib.check(_lib.lib().ssdr_knn_status(self.s_net, None))
+        return dict(xyz=st["xyz"], feat=st["feat"], idx=st["idx"], labels=st["labels"], cloud=st["cloud"], center=st["center"], probs=self.probs)
+
+    def _epoch(self, draws=None):
+        """val_steps batches; the generator runs ahead of the network by up to DEPTH batches.  Returns min(min_possibility) (:339)."""
+        self._drain()
+        gen = net = self._step_in_epoch
+        while net < self.steps:
+            while gen < self.steps and gen - net < self.DEPTH:
+                self._generate(self.draw(self.epochs, gen) if draws is None else draws(self.epochs, gen))
+                gen += 1
+            self._network()
+            net += 1
+        self._step_in_epoch = 0
+        _lib.check(_lib.lib().ssdr_knn_status(self.s_net, None))               # what the enqueue-only pyramids could not report (waits for the network's stream)
+        _lib.sync(self.s_gen)
+        new_min = float(self.d_cloud_min.to_host(self.s_gen)[: self.nc].min())
+        self.epochs += 1
+        self.min_history.append(new_min)
+        return new_min
+
+    # ---- results -------------------------------------------------------------------------------------------------------
+    def possibility(self):
+        """the map, per cloud (host copies; waits for the generator)"""
+        _lib.sync(self.s_gen)
+        p = self.d_poss.to_host(self.s_gen)
+        return [p[self.off[c]:self.off[c + 1]] for c in range(self.nc)]
+
+    def cloud_state(self):
+        """(min_possibility [C], local arg-min row [C]) (host copies; waits for the generator)"""
+        _lib.sync(self.s_gen)
+        return self.d_cloud_min.to_host(self.s_gen)[: self.nc], self.d_cloud_arg.to_host(self.s_gen)[: self.nc]
+
+    def probs_host(self):
+        _lib.sync(self.s_net)
+        return self.test_probs.to_host(self.s_net)
+
+    def _confusion(self, d_proj, labels, n, want_pred=False):
+        d_l = labels if isinstance(labels, DevArray) else DevArray.from_host(np.ascontiguousarray(labels, np.int32), self.s_net)
+        d_conf = DevArray.from_host(np.zeros((self.C, self.C), np.uint64), self.s_net); d_iou = DevArray((self.C,), np.float64)
+        d_pred = DevArray((n,), np.int32) if want_pred else None
+        _lib.check(_lib.lib().ssdr_confusion_dev(self.test_probs.ptr, self.C, d_proj.ptr if d_proj is not None else None, d_l.ptr, n,
+                                                 d_pred.ptr if want_pred else None, d_conf.ptr, d_iou.ptr, self.s_net))
+        _lib.sync(self.s_net)
+        return d_conf.to_host(self.s_net).astype(np.int64), d_iou.to_host(self.s_net), (d_pred.to_host(self.s_net) if want_pred else None)
+
+    def predictions(self):
+        """per cloud: argmax(test_probs[proj_idx]) (:381-394); needs no labels"""
+        if self.nc == 0:
+            return []
+        self._drain()
+        _, _, pred = self._confusion(self.d_proj, np.full(self.n_raw, -1, np.int32), self.n_raw, want_pred=True)
+        return [pred[self.raw_off[c]:self.raw_off[c + 1]] for c in range(self.nc)]
+
+    def evaluate(self, max_epochs=None, draws=None):
+        """The loop of RandLANet.py:305-424: whole epochs until the smallest possibility has grown by more than one vote, then the sub-cloud
+        confusion rescaled by val_proportions (:353-368), the re-projected confusion, OA and m_IoU (:377-419).  Returns (m_IoU, OA);
+        (0, 0) when max_epochs ends the loop first.  draws: a callable (epoch, step) -> the batch's draws (see draw()) in place of the seeded ones."""
+        if self.nc == 0:
+            raise ValueError("VoteTester.evaluate: no clouds")
+        if not (self.has_labels and self.has_raw_labels):
+            raise ValueError("VoteTester.evaluate: every cloud needs labels (and raw_labels with proj_idx); predictions() works without")
+        val_proportions = np.zeros(self.C, np.float32)                     # :298-303 (label_values = 0 .. C-1, none ignored)
+        for i in range(self.C):
+            val_proportions[i] = np.sum(self._raw_labels == i)
+        last_min = -0.5
+        m_iou, oa = 0, 0
+        ran = 0
+        while last_min < self.num_votes:
+            if max_epochs is not None and ran >= max_epochs:
+                break
+            new_min = self._epoch(draws)
+            ran += 1
+            if last_min + 1 < new_min:
+                last_min += 1
+                sub_conf, _, _ = self._confusion(None, self.d_labels, self.n)
+                self.sub_confusion = sub_conf
+                Cm = sub_conf.astype(np.float32)                                                       # :362
+                Cm *= np.expand_dims(val_proportions / (np.sum(Cm, axis=1) + 1e-6), 1)     # :365
+                self.sub_ious = _iou_host(Cm)
+                conf, ious, _ = self._confusion(self.d_proj, self._raw_labels, self.n_raw)
+                self.confusion, self.ious = conf, ious
+                oa = int(np.trace(conf)) / float(self.n_raw)                                           # :398-408
+                m_iou = float(np.mean(ious))                                                           # :411
+                return m_iou, oa
+        return m_iou, oa

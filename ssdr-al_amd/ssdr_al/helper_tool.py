@@ -14,6 +14,7 @@ class ConfigS3DIS:                      # helper_tool.py:46-75 (the fields the h
     sub_grid_size = 0.04
     batch_size = 6
     val_batch_size = 20
+    val_steps = 100
     sub_sampling_ratio = [4, 4, 4, 4, 2]
     d_out = [16, 64, 128, 256, 512]
     noise_init = 3.5
@@ -27,6 +28,7 @@ class ConfigSemantic3D:                 # helper_tool.py:77-117
     sub_grid_size = 0.06
     batch_size = 4
     val_batch_size = 16
+    val_steps = 100
     sub_sampling_ratio = [4, 4, 4, 4, 2]
     d_out = [16, 64, 128, 256, 512]
     noise_init = 3.5
