@@ -620,6 +620,52 @@ int ssdr_vote_tiles_dev(const float* d_points, const float* d_colors, int color_
                         void* stream);
 int ssdr_vote_tile_launches(void);
 
+/* ---- training-time generators (csrc/feed.hip; SSDR_AL_s3dis/s3dis_dataset.py:115-154, SSRD_AL_semantic3d/semantic3d_dataset_train.py:151-276) ----
+ * ssdr_feed_chain_dev: the general form of the chain above (ssdr_vote_tiles_dev = flags SSDR_FEED_GLOBAL_ROWS, no weights, no channels; the same
+ *   launches per tile).  Semantic3D_Dataset_Train.get_batch is flags = SSDR_FEED_XY_ONLY with d_class_weight and both channels.
+ *   flags: SSDR_FEED_XY_ONLY    x and y of the tile's rows are centred, z is left as it is (:182); the distance key and the possibility update
+ *                               use all three axes (:196)
+ *          SSDR_FEED_GLOBAL_ROWS d_out_idx = cloud_offsets[c] + queried_idx; clear: queried_idx itself, rows local to the tile's cloud c
+ *                               (d_out_cloud[t]), the reference's batch_pc_idx
+ *   d_class_weight f64 [num_labels] (may be NULL; needs d_labels): possibility[row] += (double)(q * q) * d_class_weight[d_labels[row]], q = 1 - d / dmax
+ *     in float32 (:196-198).  A label outside [0, num_labels) counts with weight 0 and raises bit 1 of ssdr_feed_status.
+ *   d_activation, d_pseudo f32 [n] (each may be NULL) -> d_out_activation, d_out_pseudo f32 [num_tiles,num_points], row for row what d_out_labels takes
+ *     from d_labels (the duplicates of a padded cloud included, DP.data_aug).
+ *   Refused before anything is launched: what ssdr_vote_tiles_dev refuses; d_class_weight without d_labels or with num_labels <= 0; a channel
+ *   output without its input (SSDR_ERR_INVALID).
+ * ssdr_feed_tiles_dev: num_tiles INDEPENDENT tiles (S3DIS_Dataset.spatially_regular_gen, mode "training"): tile t is cut from cloud d_tile_cloud[t]
+ *   around its point d_tile_point[t] (a cloud-local row); both are device int32 [num_tiles].  The centre = that point + d_noise[t] (device f32
+ *   [num_tiles,3]) is formed on the device in float32.  The tile is the num_points nearest rows (ascending float32 squared distance, ties by
+ *   row), through d_perm[t], padded through d_dup_u[t] when the cloud is smaller, centred on all three axes.  Outputs as above; d_out_idx holds
+ *   rows local to the tile's cloud; d_out_cloud i32 [num_tiles] (may be NULL) receives a copy of the tiles' cloud ids written in stream order,
+ *   d_out_center f32 [num_tiles,3] (may be NULL) the centres.  The same cloud may serve several tiles; all tiles go through one set of launches.
+ *   A cloud or point id out of range gives an all-zero tile (cloud id and centre included) and raises bit 2 (cloud) or bit 4 (point) of
+ *   ssdr_feed_status.  Refusals as above, and more than 65535 tiles (SSDR_ERR_UNSUPPORTED).
+ * ssdr_feed_augment_dev: tf_augment_input (:237-276) for a whole batch in one launch: columns 0..2 of d_feat [num_tiles,num_points,3+color_dim]
+ *   = float32(((x . R) * s) + noise) in float64, x = d_xyz f32 [num_tiles,num_points,3], R = [[c,-s,0],[s,c,0],[0,0,1]] with (c, s) = d_rot f64
+ *   [num_tiles,2], (x . R)_j = (x * R0j + y * R1j) + z * R2j, s = d_scale f64 [num_tiles,3] (scale times symmetry sign), noise = d_noise f64
+ *   [num_tiles,num_points,3] (may be NULL: none).  The colour columns are not touched.
+ * ssdr_feed_prefix_dev: d_out f32 [num_tiles,num_sub,3] = d_xyz[:, :num_sub] (the sub-sampled xyz levels of tf_map are per-element prefixes).
+ * ssdr_feed_status: waits for `stream`, returns the status bits the feed / chain calls on it have raised since the last call (and clears them);
+ *   SSDR_ERR_INVALID when any is set.  All other entries only enqueue. */
+#define SSDR_FEED_XY_ONLY 1
+#define SSDR_FEED_GLOBAL_ROWS 2
+int ssdr_feed_chain_dev(const float* d_points, const float* d_colors, int color_dim, const int32_t* d_labels, double* d_possibility,
+                        double* d_cloud_min, int32_t* d_cloud_arg, const int64_t* cloud_offsets, size_t num_clouds,
+                        size_t num_tiles, size_t num_points, const float* d_noise, const int32_t* d_perm, const float* d_dup_u, float color_scale,
+                        float* d_out_xyz, float* d_out_feat, int32_t* d_out_idx, int32_t* d_out_labels, int32_t* d_out_cloud, float* d_out_center,
+                        int flags, const double* d_class_weight, int num_labels, const float* d_activation, const float* d_pseudo,
+                        float* d_out_activation, float* d_out_pseudo, void* stream);
+int ssdr_feed_tiles_dev(const float* d_points, const float* d_colors, int color_dim, const int32_t* d_labels, const float* d_activation,
+                        const float* d_pseudo, const int64_t* cloud_offsets, size_t num_clouds, size_t num_tiles, size_t num_points,
+                        const int32_t* d_tile_cloud, const int32_t* d_tile_point, const float* d_noise, const int32_t* d_perm, const float* d_dup_u,
+                        float color_scale, float* d_out_xyz, float* d_out_feat, int32_t* d_out_idx, int32_t* d_out_labels, float* d_out_activation,
+                        float* d_out_pseudo, int32_t* d_out_cloud, float* d_out_center, void* stream);
+int ssdr_feed_augment_dev(const float* d_xyz, size_t num_tiles, size_t num_points, const double* d_rot, const double* d_scale, const double* d_noise,
+                          int color_dim, float* d_feat, void* stream);
+int ssdr_feed_prefix_dev(const float* d_xyz, size_t num_tiles, size_t num_points, size_t num_sub, float* d_out, void* stream);
+int ssdr_feed_status(void* stream, int32_t* out_status);
+
 /* ---- plain device memory for callers without their own allocator (tests, the ctypes mirror) ---------- */
 int ssdr_dev_alloc(size_t bytes, void** d_ptr);
 int ssdr_dev_free(void* d_ptr);

@@ -1,5 +1,9 @@
-// Test-time generator chain for gfx950: get_batch of the test datasets (S3/s3dis_dataset_test.py:97-151, the Semantic3D flavour's
-// semantic3d_dataset_test3.py:129-193) with the cloud and the centre of every tile chosen on the device.
+// Generator chain for gfx950: get_batch of the test datasets (S3/s3dis_dataset_test.py:97-151) with the cloud and the centre of every tile chosen
+// on the device.  ssdr_vote_tiles_dev is that loop as S3DIS writes it: all three axes centred, every row's update unweighted, global rows out.
+// The Semantic3D flavours differ in rules this file takes as options of the same launches (ChainArgs, vote_chain.hpp; entry ssdr_feed_chain_dev
+// in feed.hip): x and y centred only, the update weighted by the row's class (semantic3d_dataset_train.py:182, :193-198), cloud-local rows, the
+// activation / pseudo-label channels.  vote_indep_launch runs the same kernels over tiles that do not depend on each other (tile = blockIdx.y,
+// S3DIS_Dataset.spatially_regular_gen): no map, every tile's cloud and point given.
 //
 // Reference, per tile: the cloud with the smallest min_possibility (:106), its arg-min point (:108) plus noise as the centre (:112-115), the
 // num_points nearest rows (:117-122), shuffled (:125), centred (:127-128), possibility[queried] += (1 - d / max d)^2 (:132-134), the cloud's
@@ -19,8 +23,13 @@
 //                  row once: plain float64 read-modify-write, no atomics, the same bits on every run), and the histogram cleared
 //   vote_min_part  stage 1 of the cloud's new minimum: one partial (value, first row) per workgroup of VM_CHUNK rows
 // ... and one vote_pick more per call that only finishes the last tile's minimum.
+//
+// Every kernel from vote_hist to vote_gather works on record, histogram, cursors, sort words, draws and output rows number blockIdx.y: the chain
+// launches them with one row of workgroups per tile; independent tiles (vote_place writes all their records at once, nothing else before
+// vote_hist, nothing after vote_gather) with one row per tile of the batch.
 #include "ssdr_internal.hpp"
 #include "tile_body.hpp"
+#include "vote_chain.hpp"
 #include <cstring>
 #include <vector>
 
@@ -124,6 +133,7 @@ __global__ __launch_bounds__(256) void vote_pick(int has_prev, int do_pick, int 
 
 __global__ __launch_bounds__(256) void vote_hist(const VoteRec* __restrict__ rec, const float* __restrict__ pts, unsigned* hist) {
     __shared__ unsigned s_h[TS_BINS];
+    rec += blockIdx.y; hist += (size_t)blockIdx.y * TS_BINS;
     const int m = rec->m;
     if ((int)blockIdx.x * 256 >= m) return;
     const float cx = rec->cx, cy = rec->cy, cz = rec->cz;
@@ -142,6 +152,10 @@ __global__ __launch_bounds__(256) void vote_thresh(const VoteRec* __restrict__ r
     __shared__ unsigned s_h[TS_BINS + TS_BINS / 32];          // one pad word per 32 bins: a thread's stretch starts in its own bank pair
     __shared__ unsigned s_part[256];
     __shared__ unsigned s_T;
+    {
+        const size_t y = blockIdx.y;
+        rec += y; hist += y * TS_BINS; thr += 2 * y; d_cand += 2 * y; rstart += y * rstride; rcur += y * rstride; perm += y * num_points; padmap += y * num_points;
+    }
     const int tid = threadIdx.x, m = rec->m;
     constexpr int PER = TS_BINS / 256;
     auto at = [](int b) { return b + (b >> 5); };
@@ -187,8 +201,12 @@ __global__ __launch_bounds__(256) void vote_thresh(const VoteRec* __restrict__ r
 
 // candidates to their range's slots: counted per range in LDS, each range's share reserved with one global atomic per workgroup pass
 __global__ __launch_bounds__(256) void vote_compact(const VoteRec* __restrict__ rec, const float* __restrict__ pts, const unsigned* __restrict__ thr, const unsigned* __restrict__ hist,
-                                                    const unsigned* __restrict__ rstart, unsigned* rcur, int rstride, uint64_t* keys) {
+                                                    const unsigned* __restrict__ rstart, unsigned* rcur, int rstride, uint64_t* keys, size_t kstride) {
     __shared__ unsigned s_cnt[TS_RMAX], s_base[TS_RMAX];
+    {
+        const size_t y = blockIdx.y;
+        rec += y; thr += 2 * y; hist += y * TS_BINS; rstart += y * rstride; rcur += y * rstride; keys += y * kstride;
+    }
     const int m = rec->m, tid = threadIdx.x;
     if ((long long)blockIdx.x * 256 * TS_CPT >= m) return;
     const float cx = rec->cx, cy = rec->cy, cz = rec->cz;
@@ -219,7 +237,11 @@ __global__ __launch_bounds__(256) void vote_compact(const VoteRec* __restrict__ 
     }
 }
 // the same with one global atomic per candidate on its bin's cursor (clouds of more than TS_RMAX ranges)
-__global__ __launch_bounds__(256) void vote_compact_bins(const VoteRec* __restrict__ rec, const float* __restrict__ pts, const unsigned* __restrict__ thr, unsigned* hist, uint64_t* keys) {
+__global__ __launch_bounds__(256) void vote_compact_bins(const VoteRec* __restrict__ rec, const float* __restrict__ pts, const unsigned* __restrict__ thr, unsigned* hist, uint64_t* keys, size_t kstride) {
+    {
+        const size_t y = blockIdx.y;
+        rec += y; thr += 2 * y; hist += y * TS_BINS; keys += y * kstride;
+    }
     const int m = rec->m;
     const float cx = rec->cx, cy = rec->cy, cz = rec->cz;
     const float* P = pts + 3 * (size_t)rec->base;
@@ -234,8 +256,9 @@ __global__ __launch_bounds__(256) void vote_compact_bins(const VoteRec* __restri
 // one workgroup per range: bitonic network with ascending comparators only (the first step of every merge pairs a word with its mirror
 // image in the block), so slots >= n count as +infinity, are never touched, and n need not be a power of two.  Up to TS_RCAP words in LDS,
 // a longer range (one bin of more than TS_RSTEP candidates) in place in global memory.
-__global__ __launch_bounds__(256) void vote_sort(const unsigned* __restrict__ rstart, const int* __restrict__ d_cand, uint64_t* keys) {
+__global__ __launch_bounds__(256) void vote_sort(const unsigned* __restrict__ rstart, int rstride, const int* __restrict__ d_cand, uint64_t* keys, size_t kstride) {
     __shared__ uint64_t s_k[TS_RCAP];
+    rstart += (size_t)blockIdx.y * rstride; d_cand += 2 * (size_t)blockIdx.y; keys += (size_t)blockIdx.y * kstride;
     const int tid = threadIdx.x;
     const unsigned cand = (unsigned)*d_cand;
     const int nk = (int)((cand + TS_RSTEP - 1) / TS_RSTEP);
@@ -266,34 +289,103 @@ __global__ __launch_bounds__(256) void vote_sort(const unsigned* __restrict__ rs
     }
 }
 
-// the tile's rows (tile_body.hpp: shuffle, padding, centring, colours), their global row numbers, the possibility update (:132-134) over the
-// sorted prefix (its rows are distinct: one plain update each), and the histogram cleared for the next tile
+// the records of independent tiles, all at once (thread t = tile t): cloud tile_cloud[t], centre = its point tile_point[t] + noise[t] (float32,
+// s3dis_dataset.py:119-126).  An id outside its range: a record without rows (the gather writes a zero tile) and a status bit.
+__global__ __launch_bounds__(256) void vote_place(int num_tiles, int nc, const int* __restrict__ off, const float* __restrict__ pts, const int* __restrict__ tile_cloud,
+                                                  const int* __restrict__ tile_point, const float* __restrict__ noise, VoteRec* rec, int* out_cloud, float* out_center, int* status) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= num_tiles) return;
+    VoteRec r;
+    r.c = -1; r.base = 0; r.m = 0; r.cx = r.cy = r.cz = 0.f; r.pad0 = 0; r.pad1 = 0;
+    const int c = tile_cloud[t];
+    if (c < 0 || c >= nc) atomicOr(status, FEED_ST_CLOUD);
+    else {
+        const int base = off[c], m = off[c + 1] - base, p = tile_point[t];
+        if (p < 0 || p >= m) atomicOr(status, FEED_ST_POINT);
+        else {
+            r.c = c; r.base = base; r.m = m;
+            r.cx = pts[3 * ((size_t)base + p)] + noise[3 * (size_t)t];
+            r.cy = pts[3 * ((size_t)base + p) + 1] + noise[3 * (size_t)t + 1];
+            r.cz = pts[3 * ((size_t)base + p) + 2] + noise[3 * (size_t)t + 2];
+        }
+    }
+    rec[t] = r;
+    if (out_cloud) out_cloud[t] = r.c < 0 ? 0 : r.c;           // (a refused tile: zeros throughout)
+    if (out_center) { out_center[3 * (size_t)t] = r.cx; out_center[3 * (size_t)t + 1] = r.cy; out_center[3 * (size_t)t + 2] = r.cz; }
+}
+
+// what vote_gather reads and writes beyond the tile itself (all optional but hist)
+struct GatherExtra {
+    const float* act; const float* pse; float* out_act; float* out_pse;      // the channels: rows as out_lab's
+    double* possibility; const double* cw; int num_labels; int* status;       // the map (chain only), the class weights of its update
+    int flags;
+};
+
+// the tile's rows (tile_body.hpp: shuffle, padding, centring, colours), the channels and the row numbers in their final form, the possibility
+// update (:132-134; weighted: semantic3d_dataset_train.py:193-198) over the sorted prefix (its rows are distinct: one plain update each), and the
+// histogram cleared for the next tile
 __global__ __launch_bounds__(256) void vote_gather(const VoteRec* __restrict__ rec, const float* __restrict__ pts, const float* __restrict__ colors, int cdim, const int* __restrict__ labels,
-                                                   const uint64_t* __restrict__ keys, const int* __restrict__ perm, const float* __restrict__ dup_u, int num_points, float color_scale,
-                                                   float* out_xyz, float* out_feat, int* out_idx, int* out_lab, const int* __restrict__ padmap, double* possibility, unsigned* hist) {
+                                                   const uint64_t* __restrict__ keys, size_t kstride, const int* __restrict__ perm, const float* __restrict__ dup_u, int num_points, float color_scale,
+                                                   float* out_xyz, float* out_feat, int* out_idx, int* out_lab, const int* __restrict__ padmap, unsigned* hist, GatherExtra e) {
+    {
+        const size_t y = blockIdx.y, q = y * num_points;
+        rec += y; keys += y * kstride; perm += q; dup_u += q; padmap += q; hist += y * TS_BINS;
+        out_xyz += 3 * q; out_idx += q;
+        if (out_feat) out_feat += q * (3 + cdim);
+        if (out_lab) out_lab += q;
+        if (e.out_act) e.out_act += q;
+        if (e.out_pse) e.out_pse += q;
+    }
     const int base = rec->base, m = rec->m;
     const size_t o = (size_t)base;
-    tile_gather_body(pts + 3 * o, colors ? colors + o * cdim : nullptr, cdim, reinterpret_cast<const uint32_t*>(keys), &rec->m, perm, dup_u, num_points, rec->cx, rec->cy, rec->cz,
-                     color_scale, out_xyz, out_feat, out_idx, padmap, 2, -1, labels ? labels + o : nullptr, out_lab);
-    for (int r = blockIdx.x * 256 + threadIdx.x; r < num_points; r += gridDim.x * 256) out_idx[r] += base;      // (this thread wrote the row)
+    if (m <= 0) {                                              // (uniform) a refused tile: zeros; nothing was counted in its histogram
+        for (int r = blockIdx.x * 256 + threadIdx.x; r < num_points; r += gridDim.x * 256) {
+            out_xyz[3 * (size_t)r] = 0.f; out_xyz[3 * (size_t)r + 1] = 0.f; out_xyz[3 * (size_t)r + 2] = 0.f;
+            if (out_feat) for (int c = 0; c < 3 + cdim; ++c) out_feat[(size_t)r * (3 + cdim) + c] = 0.f;
+            out_idx[r] = 0;
+            if (out_lab) out_lab[r] = 0;
+            if (e.out_act) e.out_act[r] = 0.f;
+            if (e.out_pse) e.out_pse[r] = 0.f;
+        }
+        return;
+    }
+    // x - 0 = x for every x: with SSDR_FEED_XY_ONLY z goes through as it is
+    tile_gather_body(pts + 3 * o, colors ? colors + o * cdim : nullptr, cdim, reinterpret_cast<const uint32_t*>(keys), &rec->m, perm, dup_u, num_points, rec->cx, rec->cy,
+                     (e.flags & SSDR_FEED_XY_ONLY) ? 0.f : rec->cz, color_scale, out_xyz, out_feat, out_idx, padmap, 2, -1, labels ? labels + o : nullptr, out_lab);
+    const bool global_rows = (e.flags & SSDR_FEED_GLOBAL_ROWS) != 0;
+    if (global_rows || e.out_act || e.out_pse)
+        for (int r = blockIdx.x * 256 + threadIdx.x; r < num_points; r += gridDim.x * 256) {      // (this thread wrote the row)
+            const int id = out_idx[r];
+            if (e.out_act) e.out_act[r] = e.act[o + id];
+            if (e.out_pse) e.out_pse[r] = e.pse[o + id];
+            if (global_rows) out_idx[r] = id + base;
+        }
     const int avail = min(m, num_points);
-    if (avail > 0) {
+    if (e.possibility) {
         const float dmax = __uint_as_float((unsigned)(keys[avail - 1] >> 32));
-        double* P = possibility + o;
+        double* P = e.possibility + o;
         for (int r = blockIdx.x * 256 + threadIdx.x; r < avail; r += gridDim.x * 256) {
             const uint64_t w = keys[r];
             const float q = 1 - __uint_as_float((unsigned)(w >> 32)) / dmax;
-            P[(uint32_t)w] += (double)(q * q);
+            double d = (double)(q * q);
+            if (e.cw) {                                        // the float32 square widened, then times the float64 weight of the row's class
+                const int l = labels[o + (uint32_t)w];
+                double wt = 0.0;
+                if (l >= 0 && l < e.num_labels) wt = e.cw[l]; else atomicOr(e.status, FEED_ST_LABEL);
+                d = d * wt;
+            }
+            P[(uint32_t)w] += d;
         }
     }
     for (int b = blockIdx.x * 256 + threadIdx.x; b < TS_BINS; b += gridDim.x * 256) hist[b] = 0u;
 }
 
 struct VoteState {
-    DevBuf rec, part, off, keys, hist, thr, rstart, rcur, padmap;
+    DevBuf rec, part, off, keys, hist, thr, rstart, rcur, padmap, stat;
     StagingRing<int> staging;
     std::vector<int> off_host;          // the table the device holds: uploaded again only when a call brings another one
-    bool hist_clear = false;
+    size_t hist_clear = 0;              // bytes of the histogram known to be clear (vote_gather leaves it so)
+    bool stat_clear = false;
 };
 VoteState& vst(hipStream_t s) { return per_stream<VoteState>(s); }
 
@@ -329,7 +421,142 @@ int vote_upload(const char* who, VoteState& V, std::vector<int>& off, hipStream_
 }
 inline int vm_grid(int maxn) { return std::max(1, std::min((maxn + VM_CHUNK - 1) / VM_CHUNK, VM_MAXPART)); }
 
+
+// what both launchers refuse, and the scratch both need for `rows` rows of workgroups
+int chain_check(const char* who, const ChainArgs& a) {
+    if (!a.points || !a.noise || !a.perm || !a.dup_u || !a.out_xyz || !a.out_idx) { set_error("%s: bad arguments", who); return SSDR_ERR_INVALID; }
+    if (a.num_tiles == 0 || a.num_points == 0) { set_error("%s: num_tiles and num_points must be positive", who); return SSDR_ERR_INVALID; }
+    if (a.num_points > 0x3fffffff / a.num_tiles) { set_error("%s: num_tiles x num_points above 0x3fffffff rows", who); return SSDR_ERR_UNSUPPORTED; }
+    if (a.out_labels && !a.labels) { set_error("%s: labels missing", who); return SSDR_ERR_INVALID; }
+    if (a.out_feat && a.color_dim > 0 && !a.colors) { set_error("%s: colors missing", who); return SSDR_ERR_INVALID; }
+    if (a.color_dim < 0) { set_error("%s: color_dim", who); return SSDR_ERR_INVALID; }
+    if ((a.out_activation && !a.activation) || (a.out_pseudo && !a.pseudo)) { set_error("%s: a channel output without its input", who); return SSDR_ERR_INVALID; }
+    if (a.class_weight && (!a.labels || a.num_labels <= 0)) { set_error("%s: class weights need labels and num_labels > 0", who); return SSDR_ERR_INVALID; }
+    return SSDR_OK;
+}
+int chain_scratch(VoteState& V, size_t rows, int maxn, int rstride, size_t kstride, size_t num_points, hipStream_t s) {
+    SSDR_TRY(V.rec.reserve(sizeof(VoteRec) * rows)); SSDR_TRY(V.part.reserve(sizeof(MinPart) * VM_MAXPART));
+    SSDR_TRY(V.keys.reserve(8 * kstride * rows + 16)); SSDR_TRY(V.thr.reserve(8 * rows + 16));
+    SSDR_TRY(V.rstart.reserve(4 * (size_t)rstride * rows)); SSDR_TRY(V.rcur.reserve(4 * (size_t)rstride * rows)); SSDR_TRY(V.padmap.reserve(4 * num_points * rows));
+    const size_t hb = 4 * (size_t)TS_BINS * rows;
+    if (V.hist.cap < hb) V.hist_clear = 0;                   // (a new buffer)
+    SSDR_TRY(V.hist.reserve(hb));
+    if (V.hist_clear < hb) { SSDR_HIP(hipMemsetAsync(V.hist.p, 0, hb, s)); V.hist_clear = hb; }      // vote_gather leaves it clear
+    SSDR_TRY(V.stat.reserve(16));
+    if (!V.stat_clear) { SSDR_HIP(hipMemsetAsync(V.stat.p, 0, 16, s)); V.stat_clear = true; }
+    return SSDR_OK;
+}
+GatherExtra gather_extra(const ChainArgs& a, VoteState& V) {
+    GatherExtra e;
+    e.act = a.out_activation ? a.activation : nullptr; e.pse = a.out_pseudo ? a.pseudo : nullptr; e.out_act = a.out_activation; e.out_pse = a.out_pseudo;
+    e.possibility = a.possibility; e.cw = a.class_weight; e.num_labels = a.num_labels; e.status = V.stat.as<int>(); e.flags = a.flags;
+    return e;
+}
+
 }  // namespace
+
+int vote_chain_launch(const char* who, const ChainArgs& a, void* stream) {
+    // (every NULL check before any size check, as ssdr_vote_tiles_dev has always ordered them)
+    if (!a.possibility || !a.cloud_min || !a.cloud_arg || !a.out_cloud || !a.out_center) { set_error("%s: bad arguments", who); return SSDR_ERR_INVALID; }
+    SSDR_TRY(chain_check(who, a));
+    int maxn = 0;
+    std::vector<int> offh;
+    SSDR_TRY(vote_offsets(who, a.cloud_offsets, a.num_clouds, offh, maxn));
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream); VoteState& V = vst(s);
+    SSDR_TRY(vote_upload(who, V, offh, s));
+    const int N = (int)a.num_points, nc = (int)a.num_clouds, cdim = a.colors ? a.color_dim : 0;
+    const int rstride = (maxn + TS_RSTEP - 1) / TS_RSTEP + 1;
+    const int gx = vm_grid(maxn);
+    const size_t kstride = (size_t)maxn;
+    SSDR_TRY(chain_scratch(V, 1, maxn, rstride, kstride, a.num_points, s));
+    VoteRec* rec = V.rec.as<VoteRec>(); MinPart* part = V.part.as<MinPart>();
+    const int* off = V.off.as<int>();
+    unsigned* hist = V.hist.as<unsigned>(); unsigned* thr = V.thr.as<unsigned>(); int* cand = reinterpret_cast<int*>(V.thr.as<unsigned>() + 1);
+    unsigned* rstart = V.rstart.as<unsigned>(); unsigned* rcur = V.rcur.as<unsigned>();
+    uint64_t* keys = V.keys.as<uint64_t>(); int* padmap = V.padmap.as<int>();
+    const int g_hist = std::max(1, std::min((maxn + 255) / 256, 64));
+    const int g_comp = std::max(1, std::min((maxn + 256 * TS_CPT - 1) / (256 * TS_CPT), 256));
+    const int g_gath = std::max(1, std::min((N + 255) / 256, 256));
+    const int fdim = 3 + cdim;
+    const GatherExtra e0 = gather_extra(a, V);
+    for (size_t t = 0; t < a.num_tiles; ++t) {
+        const size_t q = t * a.num_points;
+        hipLaunchKernelGGL(vote_pick, dim3(1), dim3(256), 0, s, t > 0 ? 1 : 0, 1, (int)t, nc, gx, rec, (const MinPart*)part, off, a.points, a.noise, a.cloud_min, a.cloud_arg,
+                           a.out_cloud, a.out_center);
+        hipLaunchKernelGGL(vote_hist, dim3(g_hist), dim3(256), 0, s, (const VoteRec*)rec, a.points, hist);
+        hipLaunchKernelGGL(vote_thresh, dim3(1), dim3(256), 0, s, (const VoteRec*)rec, hist, N, thr, cand, rstart, rcur, rstride, a.perm + q, padmap);
+        if (rstride <= TS_RMAX)
+            hipLaunchKernelGGL(vote_compact, dim3(g_comp), dim3(256), 0, s, (const VoteRec*)rec, a.points, (const unsigned*)thr, (const unsigned*)hist, (const unsigned*)rstart, rcur, rstride, keys, kstride);
+        else hipLaunchKernelGGL(vote_compact_bins, dim3(g_hist), dim3(256), 0, s, (const VoteRec*)rec, a.points, (const unsigned*)thr, hist, keys, kstride);
+        hipLaunchKernelGGL(vote_sort, dim3(std::min(rstride, 64)), dim3(256), 0, s, (const unsigned*)rstart, rstride, (const int*)cand, keys, kstride);
+        GatherExtra e = e0;
+        if (e.out_act) e.out_act += q;
+        if (e.out_pse) e.out_pse += q;
+        hipLaunchKernelGGL(vote_gather, dim3(g_gath), dim3(256), 0, s, (const VoteRec*)rec, a.points, a.colors, cdim, a.labels, (const uint64_t*)keys, kstride, a.perm + q, a.dup_u + q, N,
+                           a.color_scale, a.out_xyz + 3 * q, a.out_feat ? a.out_feat + q * fdim : nullptr, a.out_idx + q, a.out_labels ? a.out_labels + q : nullptr,
+                           (const int*)padmap, hist, e);
+        hipLaunchKernelGGL(vote_min_part, dim3(gx), dim3(256), 0, s, (const VoteRec*)rec, off, (const double*)a.possibility, part);
+    }
+    hipLaunchKernelGGL(vote_pick, dim3(1), dim3(256), 0, s, 1, 0, 0, nc, gx, rec, (const MinPart*)part, off, a.points, a.noise, a.cloud_min, a.cloud_arg, a.out_cloud, a.out_center);
+    SSDR_HIP(hipGetLastError());
+    return SSDR_OK;
+}
+
+int vote_indep_launch(const char* who, const ChainArgs& a, void* stream) {
+    if (!a.tile_cloud || !a.tile_point) { set_error("%s: bad arguments", who); return SSDR_ERR_INVALID; }
+    SSDR_TRY(chain_check(who, a));
+    if (a.num_tiles > 65535) { set_error("%s: %zu tiles (at most 65535 in one call)", who, a.num_tiles); return SSDR_ERR_UNSUPPORTED; }
+    int maxn = 0;
+    std::vector<int> offh;
+    SSDR_TRY(vote_offsets(who, a.cloud_offsets, a.num_clouds, offh, maxn));
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream); VoteState& V = vst(s);
+    SSDR_TRY(vote_upload(who, V, offh, s));
+    const int N = (int)a.num_points, nc = (int)a.num_clouds, cdim = a.colors ? a.color_dim : 0, T = (int)a.num_tiles;
+    const int rstride = (maxn + TS_RSTEP - 1) / TS_RSTEP + 1;
+    const size_t kstride = (size_t)maxn;                     // the tiles' clouds are known on the device only: room for the largest, per tile
+    SSDR_TRY(chain_scratch(V, a.num_tiles, maxn, rstride, kstride, a.num_points, s));
+    VoteRec* rec = V.rec.as<VoteRec>();
+    unsigned* hist = V.hist.as<unsigned>(); unsigned* thr = V.thr.as<unsigned>(); int* cand = reinterpret_cast<int*>(V.thr.as<unsigned>() + 1);
+    unsigned* rstart = V.rstart.as<unsigned>(); unsigned* rcur = V.rcur.as<unsigned>();
+    uint64_t* keys = V.keys.as<uint64_t>(); int* padmap = V.padmap.as<int>();
+    const unsigned Y = (unsigned)T;
+    const int g_hist = std::max(1, std::min((maxn + 255) / 256, 64));
+    const int g_comp = std::max(1, std::min((maxn + 256 * TS_CPT - 1) / (256 * TS_CPT), 256));
+    const int g_gath = std::max(1, std::min((N + 255) / 256, 256));
+    GatherExtra e = gather_extra(a, V);
+    e.possibility = nullptr; e.cw = nullptr; e.flags &= ~SSDR_FEED_GLOBAL_ROWS;
+    hipLaunchKernelGGL(vote_place, dim3((T + 255) / 256), dim3(256), 0, s, T, nc, V.off.as<int>(), a.points, a.tile_cloud, a.tile_point, a.noise, rec, a.out_cloud, a.out_center, V.stat.as<int>());
+    hipLaunchKernelGGL(vote_hist, dim3(g_hist, Y), dim3(256), 0, s, (const VoteRec*)rec, a.points, hist);
+    hipLaunchKernelGGL(vote_thresh, dim3(1, Y), dim3(256), 0, s, (const VoteRec*)rec, hist, N, thr, cand, rstart, rcur, rstride, a.perm, padmap);
+    if (rstride <= TS_RMAX)
+        hipLaunchKernelGGL(vote_compact, dim3(g_comp, Y), dim3(256), 0, s, (const VoteRec*)rec, a.points, (const unsigned*)thr, (const unsigned*)hist, (const unsigned*)rstart, rcur, rstride, keys, kstride);
+    else hipLaunchKernelGGL(vote_compact_bins, dim3(g_hist, Y), dim3(256), 0, s, (const VoteRec*)rec, a.points, (const unsigned*)thr, hist, keys, kstride);
+    hipLaunchKernelGGL(vote_sort, dim3(std::min(rstride, 64), Y), dim3(256), 0, s, (const unsigned*)rstart, rstride, (const int*)cand, keys, kstride);
+    hipLaunchKernelGGL(vote_gather, dim3(g_gath, Y), dim3(256), 0, s, (const VoteRec*)rec, a.points, a.colors, cdim, a.labels, (const uint64_t*)keys, kstride, a.perm, a.dup_u, N,
+                       a.color_scale, a.out_xyz, a.out_feat, a.out_idx, a.out_labels, (const int*)padmap, hist, e);
+    SSDR_HIP(hipGetLastError());
+    return SSDR_OK;
+}
+
+int vote_status(void* stream, int32_t* out_status) {
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream); VoteState& V = vst(s);
+    int st = 0;
+    SSDR_HIP(hipStreamSynchronize(s));
+    if (V.stat.p && V.stat_clear) {
+        SSDR_HIP(hipMemcpy(&st, V.stat.p, 4, hipMemcpyDeviceToHost));
+        if (st) {                                              // cleared in stream order: the stream's next call finds it clear, whatever kind of stream it is
+            SSDR_HIP(hipMemsetAsync(V.stat.p, 0, 4, s));
+            SSDR_HIP(hipStreamSynchronize(s));
+        }
+    }
+    if (out_status) *out_status = st;
+    if (st) { set_error("feed: device status 0x%x (1 = a label outside the class weights, 2 = a tile's cloud id, 4 = a tile's point id out of range)", st); return SSDR_ERR_INVALID; }
+    return SSDR_OK;
+}
+
 }  // namespace ssdr
 
 using namespace ssdr;
@@ -356,52 +583,10 @@ extern "C" int ssdr_vote_tiles_dev(const float* d_points, const float* d_colors,
                                    double* d_cloud_min, int32_t* d_cloud_arg, const int64_t* cloud_offsets, size_t num_clouds,
                                    size_t num_tiles, size_t num_points, const float* d_noise, const int32_t* d_perm, const float* d_dup_u, float color_scale,
                                    float* d_out_xyz, float* d_out_feat, int32_t* d_out_idx, int32_t* d_out_labels, int32_t* d_out_cloud, float* d_out_center, void* stream) {
-    if (!d_points || !d_possibility || !d_cloud_min || !d_cloud_arg || !d_noise || !d_perm || !d_dup_u || !d_out_xyz || !d_out_idx || !d_out_cloud || !d_out_center) {
-        set_error("vote_tiles: bad arguments"); return SSDR_ERR_INVALID;
-    }
-    if (num_tiles == 0 || num_points == 0) { set_error("vote_tiles: num_tiles and num_points must be positive"); return SSDR_ERR_INVALID; }
-    if (num_points > 0x3fffffff / num_tiles) { set_error("vote_tiles: num_tiles x num_points above 0x3fffffff rows"); return SSDR_ERR_UNSUPPORTED; }
-    if (d_out_labels && !d_labels) { set_error("vote_tiles: labels missing"); return SSDR_ERR_INVALID; }
-    if (d_out_feat && color_dim > 0 && !d_colors) { set_error("vote_tiles: colors missing"); return SSDR_ERR_INVALID; }
-    if (color_dim < 0) { set_error("vote_tiles: color_dim"); return SSDR_ERR_INVALID; }
-    int maxn = 0;
-    std::vector<int> offh;
-    SSDR_TRY(vote_offsets("vote_tiles", cloud_offsets, num_clouds, offh, maxn));
-    SSDR_TRY(ensure_init());
-    hipStream_t s = pick_stream(stream); VoteState& V = vst(s);
-    SSDR_TRY(vote_upload("vote_tiles", V, offh, s));
-    const int N = (int)num_points, nc = (int)num_clouds, cdim = d_colors ? color_dim : 0;
-    const int rstride = (maxn + TS_RSTEP - 1) / TS_RSTEP + 1;
-    const int gx = vm_grid(maxn);
-    SSDR_TRY(V.rec.reserve(sizeof(VoteRec))); SSDR_TRY(V.part.reserve(sizeof(MinPart) * VM_MAXPART));
-    SSDR_TRY(V.keys.reserve(8 * (size_t)maxn + 16)); SSDR_TRY(V.hist.reserve(4 * (size_t)TS_BINS)); SSDR_TRY(V.thr.reserve(16));
-    SSDR_TRY(V.rstart.reserve(4 * (size_t)rstride)); SSDR_TRY(V.rcur.reserve(4 * (size_t)rstride)); SSDR_TRY(V.padmap.reserve(4 * num_points));
-    if (!V.hist_clear) { SSDR_HIP(hipMemsetAsync(V.hist.p, 0, 4 * (size_t)TS_BINS, s)); V.hist_clear = true; }      // vote_gather leaves it clear
-    VoteRec* rec = V.rec.as<VoteRec>(); MinPart* part = V.part.as<MinPart>();
-    const int* off = V.off.as<int>();
-    unsigned* hist = V.hist.as<unsigned>(); unsigned* thr = V.thr.as<unsigned>(); int* cand = reinterpret_cast<int*>(V.thr.as<unsigned>() + 1);
-    unsigned* rstart = V.rstart.as<unsigned>(); unsigned* rcur = V.rcur.as<unsigned>();
-    uint64_t* keys = V.keys.as<uint64_t>(); int* padmap = V.padmap.as<int>();
-    const int g_hist = std::max(1, std::min((maxn + 255) / 256, 64));
-    const int g_comp = std::max(1, std::min((maxn + 256 * TS_CPT - 1) / (256 * TS_CPT), 256));
-    const int g_gath = std::max(1, std::min((N + 255) / 256, 256));
-    const int fdim = 3 + cdim;
-    for (size_t t = 0; t < num_tiles; ++t) {
-        const size_t q = t * num_points;
-        hipLaunchKernelGGL(vote_pick, dim3(1), dim3(256), 0, s, t > 0 ? 1 : 0, 1, (int)t, nc, gx, rec, (const MinPart*)part, off, d_points, d_noise, d_cloud_min, d_cloud_arg,
-                           d_out_cloud, d_out_center);
-        hipLaunchKernelGGL(vote_hist, dim3(g_hist), dim3(256), 0, s, (const VoteRec*)rec, d_points, hist);
-        hipLaunchKernelGGL(vote_thresh, dim3(1), dim3(256), 0, s, (const VoteRec*)rec, hist, N, thr, cand, rstart, rcur, rstride, d_perm + q, padmap);
-        if (rstride <= TS_RMAX)
-            hipLaunchKernelGGL(vote_compact, dim3(g_comp), dim3(256), 0, s, (const VoteRec*)rec, d_points, (const unsigned*)thr, (const unsigned*)hist, (const unsigned*)rstart, rcur, rstride, keys);
-        else hipLaunchKernelGGL(vote_compact_bins, dim3(g_hist), dim3(256), 0, s, (const VoteRec*)rec, d_points, (const unsigned*)thr, hist, keys);
-        hipLaunchKernelGGL(vote_sort, dim3(std::min(rstride, 64)), dim3(256), 0, s, (const unsigned*)rstart, (const int*)cand, keys);
-        hipLaunchKernelGGL(vote_gather, dim3(g_gath), dim3(256), 0, s, (const VoteRec*)rec, d_points, d_colors, cdim, d_labels, (const uint64_t*)keys, d_perm + q, d_dup_u + q, N,
-                           color_scale, d_out_xyz + 3 * q, d_out_feat ? d_out_feat + q * fdim : nullptr, d_out_idx + q, d_out_labels ? d_out_labels + q : nullptr,
-                           (const int*)padmap, d_possibility, hist);
-        hipLaunchKernelGGL(vote_min_part, dim3(gx), dim3(256), 0, s, (const VoteRec*)rec, off, (const double*)d_possibility, part);
-    }
-    hipLaunchKernelGGL(vote_pick, dim3(1), dim3(256), 0, s, 1, 0, 0, nc, gx, rec, (const MinPart*)part, off, d_points, d_noise, d_cloud_min, d_cloud_arg, d_out_cloud, d_out_center);
-    SSDR_HIP(hipGetLastError());
-    return SSDR_OK;
+    ChainArgs a = {};
+    a.points = d_points; a.colors = d_colors; a.color_dim = color_dim; a.labels = d_labels; a.possibility = d_possibility; a.cloud_min = d_cloud_min; a.cloud_arg = d_cloud_arg;
+    a.cloud_offsets = cloud_offsets; a.num_clouds = num_clouds; a.num_tiles = num_tiles; a.num_points = num_points; a.noise = d_noise; a.perm = d_perm; a.dup_u = d_dup_u;
+    a.color_scale = color_scale; a.out_xyz = d_out_xyz; a.out_feat = d_out_feat; a.out_idx = d_out_idx; a.out_labels = d_out_labels; a.out_cloud = d_out_cloud;
+    a.out_center = d_out_center; a.flags = SSDR_FEED_GLOBAL_ROWS;
+    return vote_chain_launch("vote_tiles", a, stream);
 }

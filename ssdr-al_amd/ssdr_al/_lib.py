@@ -135,6 +135,11 @@ def lib():
         L.ssdr_confusion_dev.argtypes = [vp, i32, vp, vp, sz, vp, vp, vp, vp]
         L.ssdr_vote_init_dev.argtypes = [vp, vp, sz, vp, vp, vp]
         L.ssdr_vote_tiles_dev.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp]
+        L.ssdr_feed_chain_dev.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]
+        L.ssdr_feed_tiles_dev.argtypes = [vp, vp, i32, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.ssdr_feed_augment_dev.argtypes = [vp, sz, sz, vp, vp, vp, i32, vp, vp]
+        L.ssdr_feed_prefix_dev.argtypes = [vp, sz, sz, sz, vp, vp]
+        L.ssdr_feed_status.argtypes = [vp, vp]
         L.ssdr_main_stream.argtypes = [C.POINTER(vp)]
         L.ssdr_mask_regions_dev.argtypes = [vp, vp, sz, sz, vp, vp]
         L.ssdr_gather_rows_dev.argtypes = [vp, vp, sz, sz, vp, vp]

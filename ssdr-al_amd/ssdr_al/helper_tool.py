@@ -18,6 +18,7 @@ class ConfigS3DIS:                      # helper_tool.py:46-75 (the fields the h
     sub_sampling_ratio = [4, 4, 4, 4, 2]
     d_out = [16, 64, 128, 256, 512]
     noise_init = 3.5
+    train_steps = 500                   # :27 (training.TrainFeeder: one_epoch_steps)
 
 
 class ConfigSemantic3D:                 # helper_tool.py:77-117
@@ -32,6 +33,15 @@ class ConfigSemantic3D:                 # helper_tool.py:77-117
     sub_sampling_ratio = [4, 4, 4, 4, 2]
     d_out = [16, 64, 128, 256, 512]
     noise_init = 3.5
+    train_steps = 667                   # SSRD_AL_semantic3d/helper_tool.py:57: batches per epoch of get_batch
+    augment_scale_anisotropic = True    # :81-88, read by tf_augment_input (training.TrainFeeder)
+    augment_symmetries = [True, False, False]
+    augment_rotation = 'vertical'
+    augment_scale_min = 0.8
+    augment_scale_max = 1.2
+    augment_noise = 0.001
+    augment_occlusion = 'none'
+    augment_color = 0.8
 
 
 class DataProcessing:
