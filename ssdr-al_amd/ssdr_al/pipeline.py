@@ -10,7 +10,7 @@ import time
 
 import numpy as np
 
-from . import _lib, randlanet
+from . import _lib, knn, randlanet, sampler, synthetic
 from ._lib import DevArray
 from .helper_tool import ConfigS3DIS
 
@@ -48,6 +48,65 @@ class _Pairs:
 
 
 SELECTORS = ("fps", "kcenter", "edcd", "topk", "coregcn")
+
+# The words of the selection chains' int32 result buffers that the host reads.  include/ssdr_al.h defines them: d_result in the comment above
+# ssdr_gcn_fps_sampling_dev (the edcd and topk chains share its header), d_plan in the one above ssdr_gcn_fps_sharded_local_dev.
+RES_N_UNL, RES_N_PICKS, RES_STATUS = 0, 4, 5      # d_result: the candidates, the picks, the status bits
+RES_HEADER = 8                                    # the picks start here; the candidate list follows at RES_HEADER + max_select
+PLAN_N_ALL, PLAN_OVERFLOW = 8, 9                  # d_plan ([0..7] as d_result, [RES_N_PICKS] = all ranks' picks): all ranks' candidates; a rank offers more than nu_max
+PLAN_HEADER = 16                                  # the candidates per rank start here
+
+
+def _plan_gcand(world, nu_max):
+    """where d_plan's global candidate list starts: behind the header, the counts per rank and the rows of the gathered array"""
+    return PLAN_HEADER + world + world * nu_max
+
+
+def _host_rule():
+    """SSDR_SELECT_HOST_RULE: the candidate rule runs on the host (the tests' reference for the device rule)"""
+    return bool(os.environ.get("SSDR_SELECT_HOST_RULE"))
+
+
+def _capacities(nvalid, nlab, batch):
+    """What the candidate rule can produce at most when `batch` regions are asked of clouds with `nvalid` ranked and `nlab` labelled regions each:
+    (picks, cap_unl, share, cap_rows, cap_nmax, cap_sq) — the picks, the candidates, what a cloud can offer, the rows (candidates + labelled), the largest
+    cloud's rows and the sum of the clouds' squared rows.  The four cap_* size buffers and are at least 1."""
+    picks = int(min(batch, nvalid.sum()))
+    cap_unl = int(min(2 * picks, nvalid.sum()))
+    share = np.minimum(2 * picks, nvalid)                    # a cloud offers at most 2 x (its top regions) <= 2 x picks, and what it has
+    # the largest sum of squared cloud shares: fill the roomiest clouds first
+    left, sq = cap_unl, 0
+    for i in np.argsort(-(share + nlab), kind="stable"):
+        a = int(min(share[i], left)); left -= a
+        sq += (a + int(nlab[i])) ** 2
+    return picks, max(cap_unl, 1), share, max(cap_unl + int(nlab.sum()), 1), max(int((share + nlab).max()) if len(share) else 1, 1), max(int(sq), 1)
+
+
+class _Issued:
+    """One issued selection: _select_issue fills it, _select_collect consumes it and keeps the last one (comb_all, label_selected's communicator).
+    route: "device" (a one-call chain's d_result in `buf`, its picks' capacity in `max_select`), "sharded" (d_plan and the replicated picks), "topk" (`buf`
+    in the top's layout) or "host" (`picks`: a host array, or the device array the chain fills).  pairs: the candidates as (cloud, region); rooms / spin:
+    their (room id, superpoint in room), for the sharded fps / k-center routes over the GLOBAL candidate list.  keep: temporaries the enqueued chain reads.
+    Sharded extras: emu_mod (SSDR_EMULATE_WORLD: the picks index repeated rows), gcand (the global candidate list) and gorder (the global ranking) for the
+    host rule's labelling, comb / comb_n (the gathered features behind comb_all)."""
+    __slots__ = ("route", "comm", "buf", "max_select", "picks", "pairs", "rooms", "spin", "keep", "emu_mod", "gcand", "gorder", "comb", "comb_n")
+
+    def __init__(self, route, comm=None, buf=None, max_select=0):
+        self.route, self.comm, self.buf, self.max_select = route, comm, buf, int(max_select)
+        self.picks = self.pairs = self.rooms = self.spin = self.gcand = self.gorder = self.comb = None
+        self.keep, self.emu_mod, self.comb_n = [], 0, 0
+
+
+class _Picks:
+    """Where the picks of a collected selection lie, for label_selected.  layout HOST: `items` (region ids, made on the host); RESULT0 / RESULT1: in `buf`,
+    a one-call chain's d_result / the top's (the numbers are ssdr_oracle_label_items_dev's `layout`), `max_select` its picks' capacity; REPLICATED: the
+    sharded fps / k-center chain's replicated picks over the global candidate list `gcand`.  A sharded selection adds `own` (this rank's picks: their
+    positions among all picks) and, for HOST, the 64-bit walk `keys`; `refuse`: why these picks cannot be labelled."""
+    HOST, RESULT0, RESULT1, REPLICATED = -1, 0, 1, 2
+    __slots__ = ("layout", "buf", "max_select", "items", "keys", "own", "gcand", "refuse")
+
+    def __init__(self, layout, buf=None, max_select=0, items=None, keys=None, own=None, gcand=None, refuse=None):
+        self.layout, self.buf, self.max_select, self.items, self.keys, self.own, self.gcand, self.refuse = layout, buf, int(max_select), items, keys, own, gcand, refuse
 
 
 def selector_for(sampler_args, trained_gcn=False):
@@ -106,6 +165,10 @@ class HotPath:
         self.sel_stream = None      # stream of the selection chain (None = the library stream)
         self.pipelined = False      # set by Pipelined: later batches are in flight on the stage streams when a selection is collected
         self.global_order = None
+        self._dist = None           # a sharded run's static tables (_dist_setup)
+        self._pending = None        # the issued, not yet collected selection (_Issued)
+        self._collected = None      # the last collected one
+        self._last_sel = None       # where its picks lie (_Picks) until label_selected has spent them
         self.rooms = []
         self.timing = None
         self.pt_off = None          # where every cloud's points start in the concatenated arrays (LabelResult.to_host per cloud)
@@ -172,11 +235,10 @@ class HotPath:
             _lib.check(_lib.lib().ssdr_grid_subsample_status(self.front_stream, None))
         else:
             _lib.check(rc)
-        from .synthetic import superpoints_from_tile
         tiles = self.xyz.to_host()
         offs, pts, cloud = [np.zeros(1, np.int32)], [], []
         for b in range(B):
-            o, p = superpoints_from_tile(tiles[b])
+            o, p = synthetic.superpoints_from_tile(tiles[b])
             pts.append(p + b * N); offs.append(o[1:] + offs[-1][-1]); cloud.append(np.full(len(o) - 1, b, np.int32))
         labeled = {}
         sp_cloud = np.concatenate(cloud)
@@ -253,6 +315,11 @@ class HotPath:
         self.sp_size_h = np.diff(self.sp_off_h)
         self.set_labeled(labeled)
 
+    def _room_sp(self, ids):
+        """(room id, superpoint inside its room) of local region ids"""
+        c = self.sp_cloud_h[ids]
+        return np.asarray(self.room_ids, np.int64)[c], ids - np.asarray(self.sp_base, np.int64)[c]
+
     def set_labeled(self, labeled):
         """labeled[b] = the (global) ids of cloud b's regions that are already labelled (what total_obj["unlabeled"] no longer lists)"""
         cfg = self.cfg
@@ -278,7 +345,6 @@ class HotPath:
     def _draw_labelled(self, pool_sp, pool_dom_all, mine):
         """get_labeled_selection_cloudname_spidx_pointidx's draw (sampler2.py:294-302) over the pool given by its dominant labels `pool_dom_all` (all
         ranks' pools in cloud order for a sharded run; `mine` = this process's positions in it, pool_sp = their local superpoint ids)."""
-        from . import sampler
         drawn = sampler.get_labeled_selection(pool_dom_all, self.cfg.num_classes, self.round_num, np.random.RandomState(self.label_seed))
         keep = np.zeros(len(pool_dom_all), bool); keep[drawn] = True
         rows = np.asarray(pool_sp, np.int64)[keep[np.asarray(mine, np.int64)]]
@@ -297,30 +363,18 @@ class HotPath:
         nvalid = np.array([int((~self.skip_mask[base[b]:base[b + 1]]).sum()) for b in range(B)], np.int64)
         nlab = np.diff(lab_off).astype(np.int64)
         batch = self.batch_size if self.batch_size is not None else self.select_per_tile * B      # sampling()'s batch_size
-        picks = int(min(batch, nvalid.sum()))
-        cap_unl = int(min(2 * picks, nvalid.sum()))
-        share = np.minimum(2 * picks, nvalid)                    # a cloud offers at most 2 x (its top regions) <= 2 x picks, and what it has
-        cap_rows = cap_unl + int(nlab.sum())
-        # the largest sum of squared cloud shares: fill the roomiest clouds first
-        left, sq = cap_unl, 0
-        for i in np.argsort(-(share + nlab), kind="stable"):
-            a = int(min(share[i], left)); left -= a
-            sq += (a + int(nlab[i])) ** 2
+        picks, cap_unl, _, cap_rows, cap_nmax, cap_sq = _capacities(nvalid, nlab, batch)
         region = {}
         if self.selector == "edcd":      # the edcd round's rows are the candidates alone (the branch draws no labelled rows)
-            left, sq_e = cap_unl, 0
-            for i in np.argsort(-share, kind="stable"):
-                a = int(min(share[i], left)); left -= a
-                sq_e += a * a
-            region = dict(e_cap_nmax=max(int(share.max()) if B else 1, 1), e_cap_sq=max(int(sq_e), 1))
+            _, _, _, _, e_nmax, e_sq = _capacities(nvalid, np.zeros_like(nvalid), batch)
+            region = dict(e_cap_nmax=e_nmax, e_cap_sq=e_sq)
         elif self.selector == "topk":
-            region = dict(d_topk=DevArray((8 + max(min(batch, S), 1),), np.int32))
+            region = dict(d_topk=DevArray((RES_HEADER + max(min(batch, S), 1),), np.int32))
         self._sel_static = dict(region,
             lab_cloud=np.repeat(np.arange(B, dtype=np.int64), nlab), lab_sp_h=lab_sp[:-1].astype(np.int64),
             d_lab=DevArray.from_host(self.skip_mask.astype(np.uint8)), d_base=DevArray.from_host(base.astype(np.int32)),
-            d_lab_off=DevArray.from_host(lab_off), d_lab_sp=DevArray.from_host(lab_sp), n_lab=int(nlab.sum()), batch=batch, picks=picks, cap_unl=max(cap_unl, 1),
-            cap_rows=max(cap_rows, 1), cap_nmax=max(int((share + nlab).max()) if B else 1, 1), cap_sq=max(int(sq), 1),
-            d_result=DevArray((8 + picks + max(cap_rows, 1),), np.int32))
+            d_lab_off=DevArray.from_host(lab_off), d_lab_sp=DevArray.from_host(lab_sp), n_lab=int(nlab.sum()), batch=batch, picks=picks, cap_unl=cap_unl,
+            cap_rows=cap_rows, cap_nmax=cap_nmax, cap_sq=cap_sq, d_result=DevArray((RES_HEADER + picks + cap_rows,), np.int32))
 
     # ---- stages ------------------------------------------------------------------------------------------------
     def _front_end(self):
@@ -345,14 +399,10 @@ class HotPath:
         self.net.infer_dev(self.B, self.cfg.num_points, self.feat.ptr, self.xyz.ptr, [a.ptr for a in self.neigh], [a.ptr for a in self.interp],
                            self.probs.ptr, self.f32.ptr, self.stream)
 
-    def _score(self, comm=None):
-        self._score_async(comm)
-        self._score_finish(comm)
-
     def _dist_setup(self, comm):
         """Static tables of the sharded run, exchanged once (untimed): every rank's superpoint count, labelled mask, cloud and room ids.
         Global superpoint id = rank * Smax + local id (the all-gather of exchange 2 is padded to Smax rows per rank)."""
-        if getattr(self, "_dist", None) is not None and self._dist["comm"] is comm:
+        if self._dist is not None and self._dist["comm"] is comm:
             return self._dist
         W = comm.world
         # the labelled rows are drawn from the pool of ALL ranks at once (sampler2.py:294-302 draws over every cloud's labelled regions): exchange the
@@ -361,9 +411,9 @@ class HotPath:
         Pmax = max(int(npool.max()), 1)
         def padp(a):
             out = np.full(Pmax, -1, np.int64); out[: len(a)] = a; return out
-        pc = self.sp_cloud_h[self.lab_pool]
-        g_room = comm.allgather_host(padp(np.asarray(self.room_ids, np.int64)[pc])).reshape(-1)
-        g_sp = comm.allgather_host(padp(self.lab_pool - np.asarray(self.sp_base, np.int64)[pc])).reshape(-1)
+        pool_room, pool_sp = self._room_sp(self.lab_pool)
+        g_room = comm.allgather_host(padp(pool_room)).reshape(-1)
+        g_sp = comm.allgather_host(padp(pool_sp)).reshape(-1)
         g_dom = comm.allgather_host(padp(self.lab_pool_dom)).reshape(-1)
         g_rank = np.repeat(np.arange(W), Pmax); g_loc = np.tile(np.arange(Pmax), W)
         live = np.flatnonzero(g_room >= 0)
@@ -378,8 +428,9 @@ class HotPath:
             out = np.full(Smax, fill, np.int64); out[: self.S] = a; return out
         lab = comm.allgather_host(padded(self.skip_mask.astype(np.int64), 1)).reshape(-1)          # not in the ranked population (labelled / below min_size); padding counts as such
         cloud = comm.allgather_host(padded(self.sp_cloud_h, -1))                                      # local cloud index
-        room = comm.allgather_host(padded(np.asarray(self.room_ids, np.int64)[self.sp_cloud_h], -1)).reshape(-1)
-        spin = comm.allgather_host(padded(np.arange(self.S) - np.asarray(self.sp_base, np.int64)[self.sp_cloud_h], -1)).reshape(-1)
+        my_room, my_spin = self._room_sp(np.arange(self.S))
+        room = comm.allgather_host(padded(my_room, -1)).reshape(-1)
+        spin = comm.allgather_host(padded(my_spin, -1)).reshape(-1)
         Bmax = int(S_all[:, 1].max())
         gcloud = (cloud + (np.arange(W)[:, None] * Bmax)).reshape(-1)                                 # global cloud index, rank-major
         gcloud[cloud.reshape(-1) < 0] = -1
@@ -396,12 +447,8 @@ class HotPath:
         picks = int(min(batch, nvalid_all.sum()))
         T = self._sel_static
         nlab_c = np.diff(T["d_lab_off"].to_host()).astype(np.int64)
-        cap_unl = int(min(2 * picks, nvalid_c.sum()))
-        share = np.minimum(2 * picks, nvalid_c)
-        left, sq = cap_unl, 0
-        for i in np.argsort(-(share + nlab_c), kind="stable"):
-            a = int(min(share[i], left)); left -= a
-            sq += (a + int(nlab_c[i])) ** 2
+        # this rank's bounds under the GLOBAL number of picks (where its own clouds hold fewer regions than that, they offer all they have either way)
+        _, _, _, cap_rows, cap_nmax, cap_sq = _capacities(nvalid_c, nlab_c, picks)
         nu_dev = max(int(np.minimum(2 * picks, nvalid_all).max()), 1)
         rep = max(int(os.environ.get("SSDR_EMULATE_WORLD", "1")), 1)       # development: the FPS load of `rep` x the ranks (tools/gpu_emulate_world.sh)
         cap_fps = max(rep * int(min(2 * picks, nvalid_all.sum())), 1)
@@ -411,24 +458,17 @@ class HotPath:
         nl_max = int(nlab.max()) if kc else 0
         n_lab_all = int(nlab.sum()) if kc else 0
         per = nu_dev + nl_max
-        dev = dict(picks=picks, cap_rows=max(cap_unl + int(nlab_c.sum()), 1), cap_nmax=max(int((share + nlab_c).max()), 1), cap_sq=max(int(sq), 1), nu_max=nu_dev,
+        dev = dict(picks=picks, cap_rows=cap_rows, cap_nmax=cap_nmax, cap_sq=cap_sq, nu_max=nu_dev,
                    cap_fps=cap_fps, rep=rep, d_glab=DevArray.from_host((lab != 0).astype(np.uint8)), d_gbase=DevArray.from_host(gbase),
                    nl_max=nl_max, n_lab_all=n_lab_all, per=per,
                    d_send=DevArray((per, 32), np.float64), d_gath=DevArray((W, per, 32), np.float64), d_glob=DevArray((cap_fps + n_lab_all + 1, 32), np.float64),
                    d_nlab_off=DevArray.from_host(np.concatenate([[0], np.cumsum(nlab)]).astype(np.int32)), d_already=DevArray((max(n_lab_all, 1),), np.int32),
-                   d_plan=DevArray((16 + W + 2 * W * nu_dev,), np.int32), d_out=DevArray((max(rep * picks, 1),), np.int32))
+                   d_plan=DevArray((_plan_gcand(W, nu_dev) + W * nu_dev,), np.int32), d_out=DevArray((max(rep * picks, 1),), np.int32))
         if self.selector == "edcd":      # this rank's share of the edcd round: its own candidates and picks, no labelled rows
-            own = int(min(batch, nvalid_c.sum()))
-            cap_e = int(min(2 * own, nvalid_c.sum()))
-            share_e = np.minimum(2 * own, nvalid_c)
-            left, sq_e = cap_e, 0
-            for i in np.argsort(-share_e, kind="stable"):
-                a = int(min(share_e[i], left)); left -= a
-                sq_e += a * a
-            dev.update(e_picks=own, e_cap_rows=max(cap_e, 1), e_cap_nmax=max(int(share_e.max()) if self.B else 1, 1), e_cap_sq=max(int(sq_e), 1),
-                       e_result=DevArray((8 + own + max(cap_e, 1),), np.int32))
+            own, _, _, e_rows, e_nmax, e_sq = _capacities(nvalid_c, np.zeros_like(nvalid_c), batch)
+            dev.update(e_picks=own, e_cap_rows=e_rows, e_cap_nmax=e_nmax, e_cap_sq=e_sq, e_result=DevArray((RES_HEADER + own + e_rows,), np.int32))
         elif self.selector == "topk":
-            dev.update(t_result=DevArray((8 + max(min(batch, self.S), 1),), np.int32))
+            dev.update(t_result=DevArray((RES_HEADER + max(min(batch, self.S), 1),), np.int32))
         self._dist = dict(dev=dev, comm=comm, Smax=Smax, Bmax=Bmax, valid=lab == 0, gcloud=gcloud, room=room, spin=spin, batch=batch,
                           S_total=int(S_all[:, 0].sum()), n_pop=int(nvalid_all.sum()), nu_max=int(min(2 * batch, Smax)),
                           nlab=nlab, nvalid_all=nvalid_all, d_gcloud=DevArray.from_host(gcloud.astype(np.int32)),      # (the sharded labelling: every global region's global cloud)
@@ -471,14 +511,10 @@ class HotPath:
         _lib.check(L.ssdr_rank_regions_dev(D["d_all"].ptr, comm.world * D["Smax"], D["d_ord"].ptr, st))
         self.global_order = D
 
-    def _score_finish(self, comm=None):
-        """kept for callers of the two-step form: the exchanges are enqueued by _score_async and nothing waits on the host any more"""
-        return
-
-    def _candidates(self, order, valid, cloud, batch_size, with_top=False):
+    def _candidates(self, order, valid, cloud, batch_size):
         """create_file_top_and_all + the candidate rule of sampling() (sampler2.py:533-552, :745-753) on index lists: `order` ranks
         the regions by descending uncertainty, valid[i] = region i may compete (not labelled), cloud[i] = its cloud.  Returns the
-        candidates (cloud ascending, descending uncertainty inside a cloud) and their clouds, and the number to select.
+        candidates (cloud ascending, descending uncertainty inside a cloud) and their clouds, the number to select, and selected_num per cloud.
         The order is canonical: the reference's own depends on a shuffled DataLoader (sampler2.py:323) and carries no meaning."""
         order = np.asarray(order, np.int64)
         cand = order[valid[order]]                            # labelled regions never compete
@@ -493,85 +529,98 @@ class HotPath:
         first = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64) if nc else np.zeros(0, np.int64)
         pos = np.arange(len(cand)) - first[c]
         take = pos < 2 * ntop[c]                              # candidates = first 2 x selected_num of the cloud (:748)
-        if with_top:                                          # (the edcd round also needs selected_num per cloud)
-            return cand[take], c[take], int(ntop.sum()), ntop
-        return cand[take], c[take], int(ntop.sum())
+        return cand[take], c[take], int(ntop.sum()), ntop
 
     def _select(self, comm=None):
         self._select_issue(comm)
         return self._select_collect()
 
     def _select_issue(self, comm=None):
-        """everything of the selection up to the enqueued FPS chain (the host decisions and uploads happen here)"""
-        self._last_comm = comm
+        """Everything of the selection up to the enqueued FPS chain, by route: the device routes decide nothing on the host and upload nothing; the host
+        route (SSDR_SELECT_HOST_RULE, a round without picks, k-center without a labelled row) does both here.  Leaves the _Issued record in _pending."""
         if self.selector in ("edcd", "topk"):
-            return self._select_issue_region(comm)
-        L = _lib.lib()
-        st = self.sel_stream          # None: the library stream; a stream of its own lets the selections of consecutive batches overlap
-        _lib.check(L.ssdr_select_set_chamfer_mode(self.chamfer_mode))
-        T = self._sel_static
-        kc = self.selector == "kcenter"
+            self._pending = self._select_issue_region(comm)
+            return
+        _lib.check(_lib.lib().ssdr_select_set_chamfer_mode(self.chamfer_mode))
+        T, D, kc = self._sel_static, self.global_order, self.selector == "kcenter"
         if self.selector == "coregcn":
-            from . import sampler
-            if comm is not None or self.global_order is not None:
-                raise ValueError('selector="coregcn" with a communicator: the sharded form of the trained-GCN selector is not offered')
-            if T["n_lab"] == 0:
-                raise ValueError("GCN_sampling: no labelled row: the loss is a mean over an empty set (gcn.py:81-83)")
-            self._gcn_init = DevArray.from_host(sampler.gcn_init_params(self.gcn_seed), st)
-            _lib.check(L.ssdr_gcn_sampling_dev(self.f32.ptr, 32, self.cls.ptr, self.dom.ptr, self.tile_l.ptr, self.gt_dom.ptr, self.xyz.ptr, self.sp_off.ptr, self.sp_pts.ptr,
+            route, path = self._issue_coregcn, "device"
+        elif D is None and T["picks"] > 0 and (not kc or T["n_lab"] > 0) and not _host_rule():
+            route, path = self._issue_device, "device"
+        elif D is not None and D["dev"]["picks"] > 0 and (not kc or D["dev"]["n_lab_all"] > 0) and not _host_rule():
+            route, path = self._issue_sharded, "sharded-device"
+        else:
+            route, path = self._issue_host, "host"
+        self.rule_path = path
+        self._pending = route(comm)
+
+    def _issue_coregcn(self, comm):
+        L, st, T = _lib.lib(), self.sel_stream, self._sel_static
+        if comm is not None or self.global_order is not None:
+            raise ValueError('selector="coregcn" with a communicator: the sharded form of the trained-GCN selector is not offered')
+        if T["n_lab"] == 0:
+            raise ValueError("GCN_sampling: no labelled row: the loss is a mean over an empty set (gcn.py:81-83)")
+        rec = _Issued("device", None, T["d_result"], T["picks"])
+        d_init = DevArray.from_host(sampler.gcn_init_params(self.gcn_seed), st); rec.keep.append(d_init)
+        _lib.check(L.ssdr_gcn_sampling_dev(self.f32.ptr, 32, self.cls.ptr, self.dom.ptr, self.tile_l.ptr, self.gt_dom.ptr, self.xyz.ptr, self.sp_off.ptr, self.sp_pts.ptr,
+                                           self.sorted_inds.ptr, self.S, T["d_lab"].ptr, T["d_base"].ptr, self.B, T["d_lab_off"].ptr, T["d_lab_sp"].ptr,
+                                           T["n_lab"], T["batch"], d_init.ptr, self.gcn_steps, self.gcn_dropout, 1e-3, 5e-4, 1.2,
+                                           self.gcn_seed & 0xffffffffffffffff, sampler.GCN_FORMS[self.gcn_form], T["cap_rows"], T["cap_nmax"], T["cap_sq"],
+                                           T["cap_unl"], T["picks"], T["d_result"].ptr, st))
+        return rec
+
+    def _issue_device(self, comm):
+        """candidate rule + GCN_FPS_sampling enqueued as one chain: the host decides nothing and uploads nothing (the result is read in _select_collect)"""
+        L, st, T = _lib.lib(), self.sel_stream, self._sel_static          # st None: the library stream; a stream of its own lets the selections of consecutive batches overlap
+        _lib.check(L.ssdr_gcn_fps_sampling_dev(self.f32.ptr, 32, self.cls.ptr, self.dom.ptr, self.tile_l.ptr, self.gt_dom.ptr, self.xyz.ptr, self.sp_off.ptr, self.sp_pts.ptr,
                                                self.sorted_inds.ptr, self.S, T["d_lab"].ptr, T["d_base"].ptr, self.B, T["d_lab_off"].ptr, T["d_lab_sp"].ptr,
-                                               T["n_lab"], T["batch"], self._gcn_init.ptr, self.gcn_steps, self.gcn_dropout, 1e-3, 5e-4, 1.2,
-                                               self.gcn_seed & 0xffffffffffffffff, sampler.GCN_FORMS[self.gcn_form], T["cap_rows"], T["cap_nmax"], T["cap_sq"],
-                                               T["cap_unl"], T["picks"], T["d_result"].ptr, st))
-            self._pending = ("device", None)
-            self.rule_path = "device"
-            return
-        if (self.global_order is None and T["picks"] > 0 and (not kc or T["n_lab"] > 0)
-                and not os.environ.get("SSDR_SELECT_HOST_RULE")):
-            # candidate rule + GCN_FPS_sampling enqueued as one chain: the host decides nothing and uploads nothing (the result is read in _select_collect)
-            _lib.check(L.ssdr_gcn_fps_sampling_dev(self.f32.ptr, 32, self.cls.ptr, self.dom.ptr, self.tile_l.ptr, self.gt_dom.ptr, self.xyz.ptr, self.sp_off.ptr, self.sp_pts.ptr,
-                                                   self.sorted_inds.ptr, self.S, T["d_lab"].ptr, T["d_base"].ptr, self.B, T["d_lab_off"].ptr, T["d_lab_sp"].ptr,
-                                                   T["n_lab"], T["batch"], int(self.gcn_number), int(self.gcn_top), 1 if kc else 0, int(self.fps_start), T["cap_rows"], T["cap_nmax"], T["cap_sq"],
-                                                   T["cap_unl"], T["picks"], T["d_result"].ptr, st))
-            self._pending = ("device", None)
-            self.rule_path = "device"
-            return
-        if (self.global_order is not None and self.global_order["dev"]["picks"] > 0 and (not kc or self.global_order["dev"]["n_lab_all"] > 0)
-                and not os.environ.get("SSDR_SELECT_HOST_RULE")):
-            # the sharded run, still without a host decision: the rule over the global ranking + this rank's graph, the all-gather of the candidates'
-            # propagated features (exchange 3), the replicated global FPS — three enqueues, nothing read back here
-            D = self.global_order; V = D["dev"]
-            _lib.check(L.ssdr_gcn_fps_sharded_local_dev(self.f32.ptr, 32, self.cls.ptr, self.dom.ptr, self.tile_l.ptr, self.gt_dom.ptr, self.xyz.ptr, self.sp_off.ptr, self.sp_pts.ptr,
-                                                        T["d_lab_off"].ptr, T["d_lab_sp"].ptr, T["n_lab"], self.B, D["d_ord"].ptr, comm.world * D["Smax"],
-                                                        V["d_glab"].ptr, V["d_gbase"].ptr, comm.rank, comm.world, D["Smax"], D["Bmax"], D["batch"],
-                                                        int(self.gcn_number), int(self.gcn_top), V["cap_rows"], V["cap_nmax"], V["cap_sq"], V["nu_max"], V["nl_max"],
-                                                        V["d_send"].ptr, V["d_plan"].ptr, st))
-            comm.allgather_(V["d_send"], V["d_gath"], st)
-            if kc:       # BASELINE configuration 4: [candidates | labelled regions] of all ranks, the labelled ones already selected
-                _lib.check(L.ssdr_kcenter_gathered_dev(V["d_gath"].ptr, V["d_plan"].ptr, comm.world, V["nu_max"], V["nl_max"], V["d_nlab_off"].ptr, V["n_lab_all"],
-                                                       V["cap_fps"] + V["n_lab_all"] + 1, V["picks"], V["d_glob"].ptr, V["d_already"].ptr, V["d_out"].ptr, st))
-            else:
-                _lib.check(L.ssdr_fps_gathered_dev(V["d_gath"].ptr, V["d_plan"].ptr, comm.world, V["nu_max"], V["cap_fps"], V["rep"], int(self.fps_start), V["rep"] * V["picks"],
-                                                   V["d_glob"].ptr, V["d_out"].ptr, st))
-            self._pending = ("sharded", comm)
-            self.rule_path = "sharded-device"
-            return
-        self.rule_path = "host"
-        if self.global_order is None:          # (the D2H below runs on the selection stream, which already waits for the scoring stream's work)
-            cand, ccloud, sampling_batch = self._candidates(self.sorted_inds.to_host(st), ~self.skip_mask, self.sp_cloud_h, self._sel_static["batch"])
+                                               T["n_lab"], T["batch"], int(self.gcn_number), int(self.gcn_top), 1 if self.selector == "kcenter" else 0, int(self.fps_start),
+                                               T["cap_rows"], T["cap_nmax"], T["cap_sq"], T["cap_unl"], T["picks"], T["d_result"].ptr, st))
+        return _Issued("device", comm, T["d_result"], T["picks"])
+
+    def _issue_sharded(self, comm):
+        """the sharded run, still without a host decision: the rule over the global ranking + this rank's graph, the all-gather of the candidates'
+        propagated features (exchange 3), the replicated global FPS — three enqueues, nothing read back here"""
+        L, st, T, kc = _lib.lib(), self.sel_stream, self._sel_static, self.selector == "kcenter"
+        D = self.global_order; V = D["dev"]
+        _lib.check(L.ssdr_gcn_fps_sharded_local_dev(self.f32.ptr, 32, self.cls.ptr, self.dom.ptr, self.tile_l.ptr, self.gt_dom.ptr, self.xyz.ptr, self.sp_off.ptr, self.sp_pts.ptr,
+                                                    T["d_lab_off"].ptr, T["d_lab_sp"].ptr, T["n_lab"], self.B, D["d_ord"].ptr, comm.world * D["Smax"],
+                                                    V["d_glab"].ptr, V["d_gbase"].ptr, comm.rank, comm.world, D["Smax"], D["Bmax"], D["batch"],
+                                                    int(self.gcn_number), int(self.gcn_top), V["cap_rows"], V["cap_nmax"], V["cap_sq"], V["nu_max"], V["nl_max"],
+                                                    V["d_send"].ptr, V["d_plan"].ptr, st))
+        comm.allgather_(V["d_send"], V["d_gath"], st)
+        if kc:       # BASELINE configuration 4: [candidates | labelled regions] of all ranks, the labelled ones already selected
+            _lib.check(L.ssdr_kcenter_gathered_dev(V["d_gath"].ptr, V["d_plan"].ptr, comm.world, V["nu_max"], V["nl_max"], V["d_nlab_off"].ptr, V["n_lab_all"],
+                                                   V["cap_fps"] + V["n_lab_all"] + 1, V["picks"], V["d_glob"].ptr, V["d_already"].ptr, V["d_out"].ptr, st))
+        else:
+            _lib.check(L.ssdr_fps_gathered_dev(V["d_gath"].ptr, V["d_plan"].ptr, comm.world, V["nu_max"], V["cap_fps"], V["rep"], int(self.fps_start), V["rep"] * V["picks"],
+                                               V["d_glob"].ptr, V["d_out"].ptr, st))
+        rec = _Issued("sharded", comm, V["d_plan"], V["picks"])
+        rec.picks = V["d_out"]
+        return rec
+
+    def _issue_host(self, comm):
+        """The candidate rule on the host, then the batched graph, the propagation and the FPS / k-center chain enqueued over uploaded index tables."""
+        L, st, T, D, kc = _lib.lib(), self.sel_stream, self._sel_static, self.global_order, self.selector == "kcenter"
+        rec = _Issued("host", comm)
+        if D is None:          # (the D2H below runs on the selection stream, which already waits for the scoring stream's work)
+            cand, ccloud, sampling_batch, _ = self._candidates(self.sorted_inds.to_host(st), ~self.skip_mask, self.sp_cloud_h, T["batch"])
             unl_c, unl_s = np.asarray(ccloud, np.int64), np.asarray(cand, np.int64)
-            gl_room = np.asarray(self.room_ids, np.int64)[ccloud]; gl_sp = cand - np.asarray(self.sp_base, np.int64)[ccloud]
+            rec.rooms, rec.spin = self._room_sp(unl_s)
             counts_r = None
         else:       # every rank derives the global candidate list from the global ranking, then keeps its own rows
-            D = self.global_order
-            gcand, gcloud, sampling_batch = self._candidates(D["d_ord"].to_host(st), D["valid"], D["gcloud"], D["batch"])
-            self._gcand_h = gcand                                # (label_selected(comm=): the picks index this list)
+            gcand, gcloud, sampling_batch, _ = self._candidates(D["d_ord"].to_host(st), D["valid"], D["gcloud"], D["batch"])
+            rec.gcand = gcand                                    # (label_selected(comm=): the picks index this list)
             r_of = gcand // D["Smax"]
             counts_r = np.bincount(r_of, minlength=comm.world)
             mine = r_of == comm.rank
             unl_c, unl_s = (gcloud[mine] - comm.rank * D["Bmax"]).astype(np.int64), (gcand[mine] - comm.rank * D["Smax"]).astype(np.int64)
-            gl_room, gl_sp = D["room"][gcand], D["spin"][gcand]
-        unl = list(zip(unl_c.tolist(), unl_s.tolist()))          # (cloud, superpoint) of this rank's candidates
+            rec.rooms, rec.spin = D["room"][gcand], D["spin"][gcand]
+        rec.pairs = unl = _Pairs(unl_c, unl_s)                    # (cloud, superpoint) of this rank's candidates
+        if sampling_batch == 0:      # nothing to select anywhere (the global count: every rank of a sharded run returns here, before any exchange)
+            rec.picks = np.zeros(0, np.int32)
+            return rec
+        keep = rec.keep
         lab_c, lab_s = T["lab_cloud"], T["lab_sp_h"]              # the labelled regions, cloud by cloud, ascending superpoint id (static)
         sel = np.concatenate([unl_s, lab_s]).astype(np.int32)
         # every cloud's chamfer graph and propagation hop in one batched call (rows grouped cloud by cloud)
@@ -585,7 +634,7 @@ class HotPath:
         n_unl = len(unl_s)
         src = np.zeros(0, np.int32)
         if counts_r is not None:     # exchange 3 is padded to nu_max rows per rank: positions of the real rows in the gathered array
-            src = np.concatenate([r * self.global_order["nu_max"] + np.arange(c) for r, c in enumerate(counts_r)]).astype(np.int32)
+            src = np.concatenate([r * D["nu_max"] + np.arange(c) for r, c in enumerate(counts_r)]).astype(np.int32)
         # ONE upload for all the small index tables (each separate copy is a host round trip behind the kernels in flight)
         parts = [sel, sel[order], order, coff, boff.view(np.int32), src]
         offs = np.cumsum([0] + [(len(p) + 3) // 4 * 4 for p in parts])           # 16-byte aligned pieces
@@ -594,17 +643,16 @@ class HotPath:
             pack[o:o + len(p)] = p
         d_pack = DevArray.from_host(pack, st)
         d_sel, d_gsel, d_rows, d_coff, d_boff, d_src = (d_pack.ptr + 4 * int(o) for o in offs[:-1])
-        rows = max(len(sel), self.global_order["nu_max"] if counts_r is not None else 0)
+        rows = max(len(sel), D["nu_max"] if counts_r is not None else 0)
         d_mf = DevArray((len(sel), 32), np.float32)
         d_v = DevArray((len(sel), 32), np.float64); d_comb = DevArray((rows, 32), np.float64)
         d_tmp = [DevArray(d_v.shape, np.float64), DevArray(d_v.shape, np.float64)]
         # compute_features (sampler2.py:333, :339): the candidates' members by the predicted classes, the labelled regions' by the ground truth (:288-291)
-        nu_rows = len(unl_s)
-        if nu_rows:
-            _lib.check(L.ssdr_segment_mean_features_dev(self.f32.ptr, 32, self.cls.ptr, self.dom.ptr, self.sp_off.ptr, self.sp_pts.ptr, d_sel, nu_rows, d_mf.ptr, st))
-        if len(sel) > nu_rows:
-            _lib.check(L.ssdr_segment_mean_features_dev(self.f32.ptr, 32, self.tile_l.ptr, self.gt_dom.ptr, self.sp_off.ptr, self.sp_pts.ptr, d_sel + 4 * nu_rows,
-                                                        len(sel) - nu_rows, d_mf.ptr + 4 * 32 * nu_rows, st))
+        if n_unl:
+            _lib.check(L.ssdr_segment_mean_features_dev(self.f32.ptr, 32, self.cls.ptr, self.dom.ptr, self.sp_off.ptr, self.sp_pts.ptr, d_sel, n_unl, d_mf.ptr, st))
+        if len(sel) > n_unl:
+            _lib.check(L.ssdr_segment_mean_features_dev(self.f32.ptr, 32, self.tile_l.ptr, self.gt_dom.ptr, self.sp_off.ptr, self.sp_pts.ptr, d_sel + 4 * n_unl,
+                                                        len(sel) - n_unl, d_mf.ptr + 4 * 32 * n_unl, st))
         # float32 -> float64 as np.concatenate / np.matmul promote it (V and the running sum comb start as the same values)
         _lib.check(L.ssdr_widen_f32_f64_dev(d_mf.ptr, len(sel) * 32, d_v.ptr, d_comb.ptr, st))
         d_cen = DevArray((ntot, 3), np.float64); d_dir = DevArray((nsq,), np.float64); d_adj = DevArray((nsq,), np.float64)
@@ -615,13 +663,10 @@ class HotPath:
             dst = d_tmp[hop & 1]
             _lib.check(L.ssdr_propagate_batch_dev(d_adj.ptr, d_coff, d_boff, len(clouds), nmax, d_rows, src_v.ptr, 32, dst.ptr, d_comb.ptr, st))
             src_v = dst
-        keep = [d_pack, d_cen, d_dir, d_adj, d_v, d_tmp, d_mf, d_comb]
-        self.unl_cloud_ids, self.unl_sp = gl_room, gl_sp          # (room id, superpoint inside its room) of every candidate, global order
+        keep += [d_pack, d_cen, d_dir, d_adj, d_v, d_tmp, d_mf, d_comb]
         n_lab = len(lab_s)
         if comm is not None:                                 # exchange 3: the candidates' propagated features, on the selection stream
-            D = self.global_order
-            kc = self.selector == "kcenter"                  # k-center also needs the labelled regions' rows of every rank
-            nl_max = int(D["nlab"].max()) if kc else 0
+            nl_max = int(D["nlab"].max()) if kc else 0       # k-center also needs the labelled regions' rows of every rank
             per = D["nu_max"] + nl_max
             d_send = d_comb
             if kc:                                           # [candidates, padded to nu_max | labelled, padded to nl_max]
@@ -642,7 +687,7 @@ class HotPath:
             _lib.check(L.ssdr_gather_rows_dev(d_gath.ptr, d_src, n_rows, 32 * 8, d_glob.ptr, st))
             keep += [d_gath, d_glob]
             d_comb = d_glob
-            self._comb_dev, self._comb_n = d_glob, n_rows
+            rec.comb, rec.comb_n = d_glob, n_rows
         emu = int(os.environ.get("SSDR_EMULATE_WORLD", "0"))
         if emu > 1 and comm is not None and self.selector != "kcenter":
             # development: the FPS LOAD of `emu` ranks on one GPU (the replicated global chain is N^2: N x the rows, N x the picks) — the rows are
@@ -652,76 +697,79 @@ class HotPath:
             _lib.check(L.ssdr_gather_rows_dev(d_comb.ptr, d_idx.ptr, emu * n_unl, 32 * 8, d_big.ptr, st))
             keep += [d_idx, d_big]
             d_comb, n_unl, sampling_batch = d_big, emu * n_unl, emu * sampling_batch
-            self._emu_mod = len(idx) // emu
-        d_out = DevArray((sampling_batch,), np.int32)
+            rec.emu_mod = len(idx) // emu
+        rec.picks = d_out = DevArray((sampling_batch,), np.int32)
         if self.selector == "kcenter":
             d_already = DevArray.from_host((n_unl + np.arange(n_lab)).astype(np.int32), st); keep.append(d_already)
             _lib.check(L.ssdr_kcenter_dev(d_comb.ptr, n_unl + n_lab, 32, d_already.ptr, n_lab, sampling_batch, d_out.ptr, st))
         else:
             _lib.check(L.ssdr_fps_dev(d_comb.ptr, n_unl, 32, int(self.fps_start), sampling_batch, d_out.ptr, st))
-        self._keep = keep
-        self._pending = (d_out, unl)
+        return rec
 
     def _select_issue_region(self, comm=None):
-        """_select_issue of the "edcd" and "topk" selectors.  Device rule (default): one enqueue-only call over the ranking, single-process or sharded,
-        nothing read back here.  SSDR_SELECT_HOST_RULE: the candidate rule / the top on the host, then (edcd) the batched graph and the batched FPS.
-        (sel, unl) keep their contract: edcd's unl = the candidate list (cloud ascending, descending uncertainty inside a cloud) and sel indexes it;
-        topk's unl = the top regions in rank order and sel = arange.  A sharded rank returns its own clouds' share."""
-        L = _lib.lib()
-        st = self.sel_stream
-        T = self._sel_static
-        edcd = self.selector == "edcd"
-        D = self.global_order
-        if not os.environ.get("SSDR_SELECT_HOST_RULE"):
-            if D is None and edcd:
-                _lib.check(L.ssdr_edcd_sampling_dev(self.xyz.ptr, self.sp_off.ptr, self.sp_pts.ptr, self.sorted_inds.ptr, self.S, T["d_lab"].ptr, T["d_base"].ptr, self.B,
-                                                    T["batch"], T["cap_unl"], T["e_cap_nmax"], T["e_cap_sq"], T["picks"], T["d_result"].ptr, st))
-                self._pending = ("device", (T["d_result"], T["picks"]))
-            elif D is None:
-                _lib.check(L.ssdr_topk_regions_dev(self.sorted_inds.ptr, self.S, T["d_lab"].ptr, T["batch"], 0, self.S, T["d_topk"].ptr, T["d_topk"].ptr + 32, st))
-                self._pending = ("topk", T["d_topk"])
-            else:
-                V = D["dev"]; lo = comm.rank * D["Smax"]
-                if edcd:
-                    _lib.check(L.ssdr_edcd_sampling_sharded_dev(self.xyz.ptr, self.sp_off.ptr, self.sp_pts.ptr, self.B, D["d_ord"].ptr, comm.world * D["Smax"], V["d_glab"].ptr,
-                                                                V["d_gbase"].ptr, comm.rank, comm.world, D["Smax"], D["Bmax"], D["batch"], V["e_cap_rows"], V["e_cap_nmax"],
-                                                                V["e_cap_sq"], V["e_picks"], V["e_result"].ptr, st))
-                    self._pending = ("device", (V["e_result"], V["e_picks"]))
-                else:
-                    _lib.check(L.ssdr_topk_regions_dev(D["d_ord"].ptr, comm.world * D["Smax"], V["d_glab"].ptr, D["batch"], lo, lo + self.S, V["t_result"].ptr,
-                                                       V["t_result"].ptr + 32, st))
-                    self._pending = ("topk", V["t_result"])
-            self.rule_path = "device" if D is None else "sharded-device"
-            return
-        self.rule_path = "host"
+        """_select_issue of the "edcd" and "topk" selectors; returns the _Issued record.  Device rule (default): one enqueue-only call over the ranking,
+        single-process or sharded, nothing read back here.  SSDR_SELECT_HOST_RULE: the candidate rule / the top on the host, then (edcd) the batched graph
+        and the batched FPS.  (sel, unl) keep their contract: edcd's unl = the candidate list (cloud ascending, descending uncertainty inside a cloud) and
+        sel indexes it; topk's unl = the top regions in rank order and sel = arange.  A sharded rank returns its own clouds' share."""
+        if _host_rule():
+            route, path = self._issue_region_host, "host"
+        elif self.global_order is None:
+            route, path = self._issue_region_device, "device"
+        else:
+            route, path = self._issue_region_sharded, "sharded-device"
+        self.rule_path = path
+        return route(comm)
+
+    def _issue_region_device(self, comm):
+        L, st, T = _lib.lib(), self.sel_stream, self._sel_static
+        if self.selector == "edcd":
+            _lib.check(L.ssdr_edcd_sampling_dev(self.xyz.ptr, self.sp_off.ptr, self.sp_pts.ptr, self.sorted_inds.ptr, self.S, T["d_lab"].ptr, T["d_base"].ptr, self.B,
+                                                T["batch"], T["cap_unl"], T["e_cap_nmax"], T["e_cap_sq"], T["picks"], T["d_result"].ptr, st))
+            return _Issued("device", comm, T["d_result"], T["picks"])
+        _lib.check(L.ssdr_topk_regions_dev(self.sorted_inds.ptr, self.S, T["d_lab"].ptr, T["batch"], 0, self.S, T["d_topk"].ptr, T["d_topk"].ptr + 4 * RES_HEADER, st))
+        return _Issued("topk", comm, T["d_topk"], int(T["d_topk"].shape[0]) - RES_HEADER)
+
+    def _issue_region_sharded(self, comm):
+        L, st, D = _lib.lib(), self.sel_stream, self.global_order
+        V = D["dev"]; lo = comm.rank * D["Smax"]
+        if self.selector == "edcd":
+            _lib.check(L.ssdr_edcd_sampling_sharded_dev(self.xyz.ptr, self.sp_off.ptr, self.sp_pts.ptr, self.B, D["d_ord"].ptr, comm.world * D["Smax"], V["d_glab"].ptr,
+                                                        V["d_gbase"].ptr, comm.rank, comm.world, D["Smax"], D["Bmax"], D["batch"], V["e_cap_rows"], V["e_cap_nmax"],
+                                                        V["e_cap_sq"], V["e_picks"], V["e_result"].ptr, st))
+            return _Issued("device", comm, V["e_result"], V["e_picks"])
+        _lib.check(L.ssdr_topk_regions_dev(D["d_ord"].ptr, comm.world * D["Smax"], V["d_glab"].ptr, D["batch"], lo, lo + self.S, V["t_result"].ptr,
+                                           V["t_result"].ptr + 4 * RES_HEADER, st))
+        return _Issued("topk", comm, V["t_result"], int(V["t_result"].shape[0]) - RES_HEADER)
+
+    def _issue_region_host(self, comm):
+        L, st, T, D = _lib.lib(), self.sel_stream, self._sel_static, self.global_order
+        rec = _Issued("host", comm)
         if D is None:
             order, valid, cloud, batch, sub_c, sub_s = self.sorted_inds.to_host(st), ~self.skip_mask, self.sp_cloud_h, T["batch"], 0, 0
-            room = np.asarray(self.room_ids, np.int64)[self.sp_cloud_h]
-            spin = np.arange(self.S) - np.asarray(self.sp_base, np.int64)[self.sp_cloud_h]
+            room, spin = self._room_sp(np.arange(self.S))
         else:
             order, valid, cloud, batch, sub_c, sub_s = D["d_ord"].to_host(st), D["valid"], D["gcloud"], D["batch"], comm.rank * D["Bmax"], comm.rank * D["Smax"]
             room, spin = D["room"], D["spin"]
-        order = np.asarray(order, np.int64)
-        self._gorder_h = order
-        if not edcd:                          # the top: the first batch_size regions of the population in rank order, this rank's own kept
+        rec.gorder = order = np.asarray(order, np.int64)
+        if self.selector == "topk":           # the top: the first batch_size regions of the population in rank order, this rank's own kept
             top = order[valid[order]][: batch]
             top = top[(top >= sub_s) & (top < sub_s + self.S)]
             loc = top - sub_s
-            self.unl_cloud_ids, self.unl_sp = room[top], spin[top]
-            self._pending = (np.arange(len(loc), dtype=np.int32), _Pairs(self.sp_cloud_h[loc], loc))
-            return
-        cand, ccloud, _, ntop = self._candidates(order, valid, cloud, batch, with_top=True)
+            rec.rooms, rec.spin = room[top], spin[top]
+            rec.picks, rec.pairs = np.arange(len(loc), dtype=np.int32), _Pairs(self.sp_cloud_h[loc], loc)
+            return rec
+        cand, ccloud, _, ntop = self._candidates(order, valid, cloud, batch)
         mine = (cand >= sub_s) & (cand < sub_s + self.S)
         gcand = cand[mine]
         cand, ccloud = gcand - sub_s, ccloud[mine] - sub_c
         ntop = np.concatenate([ntop, np.zeros(max(sub_c + self.B - len(ntop), 0), np.int64)])[sub_c: sub_c + self.B]
-        unl = _Pairs(ccloud, cand)
-        self.unl_cloud_ids, self.unl_sp = room[gcand], spin[gcand]
+        rec.pairs = _Pairs(ccloud, cand)
+        rec.rooms, rec.spin = room[gcand], spin[gcand]
         live = np.flatnonzero(ntop > 0)       # the clouds with picks are the clouds with candidates (a cloud offers min(2 x its picks, its regions))
         picks = int(ntop.sum())
         if picks == 0:
-            self._pending = (np.zeros(0, np.int32), unl)
-            return
+            rec.picks = np.zeros(0, np.int32)
+            return rec
         n_c = np.bincount(ccloud, minlength=self.B)[live].astype(np.int64)
         if int(n_c.max()) > 8192:
             raise RuntimeError("edcd: a cloud has %d candidates; the batched farthest_superpoint_sample takes at most 8192" % int(n_c.max()))
@@ -735,125 +783,118 @@ class HotPath:
         _lib.check(L.ssdr_cloud_graph_batch_dev(self.xyz.ptr, self.sp_off.ptr, self.sp_pts.ptr, d_sel.ptr, d_coff.ptr, d_boff.ptr, len(live), ntot, nmax, 0,
                                                 d_cen.ptr, d_dir.ptr, d_adj.ptr, st))
         _lib.check(L.ssdr_select_set_chamfer_mode(self.chamfer_mode))
-        d_out = DevArray((picks,), np.int32)
+        rec.picks = d_out = DevArray((picks,), np.int32)
         _lib.check(L.ssdr_edcd_fps_batch_dev(d_cen.ptr, d_dir.ptr, d_coff.ptr, d_boff.ptr, d_ntop.ptr, len(live), nmax, picks, d_out.ptr, None, st))
-        self._keep = [d_sel, d_coff, d_boff, d_ntop, d_cen, d_dir, d_adj]
-        self._pending = (d_out, unl)
+        rec.keep += [d_sel, d_coff, d_boff, d_ntop, d_cen, d_dir, d_adj]
+        return rec
 
     @property
     def comb_all(self):
-        """the gathered candidate features of the last sharded step (tests)"""
+        """the gathered candidate features of the last collected sharded selection (tests)"""
         _lib.sync()
-        return self._comb_dev.to_host()[: self._comb_n]
+        return self._collected.comb.to_host()[: self._collected.comb_n]
 
     def _select_collect(self):
         """wait for the FPS chain of _select_issue and read the selection back"""
-        d_out, unl = self._pending
-        self._pending = None
-        if isinstance(d_out, str) and d_out == "sharded":     # the sharded device-side rule: the plan (counts, global candidate list) and the picks
-            comm = unl
-            D = self.global_order; V = D["dev"]; W = comm.world
-            plan = V["d_plan"].to_host(self.sel_stream)          # waits for the selection stream alone
-            sel = V["d_out"].to_host(self.sel_stream)
-            _lib.check(_lib.lib().ssdr_select_status(self.sel_stream, None))
-            if plan[5] or plan[9]:
-                raise RuntimeError("gcn_fps_sharded: the candidate rule produced more rows than the capacities allow (status %d, %d)" % (int(plan[5]), int(plan[9])))
-            n_g = int(plan[8])
-            gcand = plan[16 + W + W * V["nu_max"]: 16 + W + W * V["nu_max"] + n_g].astype(np.int64)
-            mine = gcand // D["Smax"] == comm.rank
-            loc = gcand[mine] - comm.rank * D["Smax"]
-            unl = list(zip(self.sp_cloud_h[loc].tolist(), loc.tolist()))
-            self.unl_cloud_ids, self.unl_sp = D["room"][gcand], D["spin"][gcand]
-            self._comb_dev, self._comb_n = V["d_glob"], n_g + (V["n_lab_all"] if self.selector == "kcenter" else 0)
-            if V["rep"] > 1:
-                self._emu_mod = n_g
-            where = dict(layout="picks", gcand=gcand)
-        elif isinstance(d_out, str) and d_out == "topk":     # the top regions of the ranking (this rank's own): sel = arange
-            where = dict(layout=1, buf=unl, max_select=int(unl.shape[0]) - 8)
-            res = unl.to_host(self.sel_stream)
-            _lib.check(_lib.lib().ssdr_select_status(self.sel_stream, None))
-            loc = res[8:8 + int(res[0])].astype(np.int64)
-            sel = np.arange(len(loc), dtype=np.int32)
-            ccloud = self.sp_cloud_h[loc]
-            unl = _Pairs(ccloud, loc)
-            self.unl_cloud_ids = np.asarray(self.room_ids, np.int64)[ccloud]; self.unl_sp = loc - np.asarray(self.sp_base, np.int64)[ccloud]
-        elif isinstance(d_out, str):                          # the device-side rule: counts, picks and the candidate list in one read-back
-            T = self._sel_static
-            d_res, max_select = (T["d_result"], T["picks"]) if unl is None else unl      # (the edcd chains name their result buffer)
-            where = dict(layout=0, buf=d_res, max_select=int(max_select))
-            res = d_res.to_host(self.sel_stream)             # waits for the selection stream alone
-            # from ~20 tiles per GPU on the chain's FPS / k-center is a cooperative launch: one that was not co-resident reports it here
-            _lib.check(_lib.lib().ssdr_select_status(self.sel_stream, None))
-            if self.selector == "coregcn":
-                from . import sampler
-                self.gcn_info = info = self.gcn_rows(info_only=True)
-                sampler.gcn_status_check(info, self.room_ids)
-            if res[5] & ~3:
-                raise RuntimeError("edcd_sampling: %s (status %d): nothing was selected" % (
-                    "a cloud has more than 8192 candidates" if res[5] & 4 else "the picks do not fit the capacities", int(res[5])))
-            if res[5]:
-                raise RuntimeError("gcn_fps_sampling: the candidate rule produced more rows than the capacities allow (status %d)" % int(res[5]))
-            n_unl, picks = int(res[0]), int(res[4])
-            sel = res[8:8 + picks].copy()
-            cand = res[8 + max_select: 8 + max_select + n_unl].astype(np.int64)
-            ccloud = self.sp_cloud_h[cand]
-            unl = _Pairs(ccloud, cand)                               # (20 000 candidates in one AL round: the tuples are built when somebody reads them)
-            self.unl_cloud_ids = np.asarray(self.room_ids, np.int64)[ccloud]; self.unl_sp = cand - np.asarray(self.sp_base, np.int64)[ccloud]
-        elif isinstance(d_out, np.ndarray):                   # (decided on the host: the top of the host rule, a round without picks)
-            sel = d_out
-            where = "host"
-            _lib.check(_lib.lib().ssdr_select_status(self.sel_stream, None))
-        else:
-            where = "host"
-            sel = d_out.to_host(self.sel_stream)             # waits for the selection stream alone
-            # a cooperative (multi-workgroup) FPS / k-center launch that was not co-resident reports it here instead of returning a wrong selection
-            _lib.check(_lib.lib().ssdr_select_status(self.sel_stream, None))
+        rec, self._pending = self._pending, None
+        # Waits for the selection stream alone.  From ~20 tiles per GPU on the chain's FPS / k-center is a cooperative (multi-workgroup) launch: one that
+        # was not co-resident reports it here, before its result is looked at, instead of returning a wrong selection
+        _lib.check(_lib.lib().ssdr_select_status(self.sel_stream, None))
+        sel, unl, where = {"device": self._collect_device, "sharded": self._collect_sharded, "topk": self._collect_topk, "host": self._collect_host}[rec.route](rec)
         # the device-flavour KNN calls cannot report what their kernels found (overflowed kd queue / node table / level limit, hand-over
         # list): ask once per batch, here where the host waits anyway — without waiting for the pyramids of the LATER batches that the
         # KNN stream already holds (the finished calls' tickets are looked at; Pipelined.finish / the sequential step wait for all)
-        from . import knn as _knn
-        _knn.knn_status(self.knn_stream if self.knn_stream is not None else self.stream, wait=not self.pipelined)
+        knn.knn_status(self.knn_stream if self.knn_stream is not None else self.stream, wait=not self.pipelined)
         if not self.pipelined:                               # sequential use: the front end of this batch has finished, ask it too
             _lib.check(_lib.lib().ssdr_grid_subsample_status(self.front_stream if self.front_stream is not None else self.stream, None))
         if len(sel) and int(np.min(sel)) < 0:                # (an aborted chain leaves -1 picks: never index the candidate list with them)
             raise RuntimeError("selection: the FPS / k-center chain left unset picks (an aborted cooperative launch)")
-        if getattr(self, "_emu_mod", 0):                    # (SSDR_EMULATE_WORLD: the picks index the repeated rows)
-            sel = sel % self._emu_mod
+        if rec.emu_mod:                                      # (SSDR_EMULATE_WORLD: the picks index the repeated rows)
+            sel = sel % rec.emu_mod
         si = np.asarray(sel, np.int64)
-        if getattr(self, "_last_comm", None) is not None:
-            where = self._sharded_where(where, si, unl, self._last_comm)
-        elif where == "host":        # decided on the host: the picks as global region ids (label_selected uploads them)
-            ids = unl.b if isinstance(unl, _Pairs) else np.asarray([u[1] for u in unl], np.int64)
-            where = dict(layout=None, items=np.asarray(ids, np.int64).reshape(-1)[si])
-        self._last_sel = where      # where the picks of this selection lie, for label_selected
-        self._selected = _Pairs(np.asarray(self.unl_cloud_ids)[si], np.asarray(self.unl_sp)[si])      # (room id, superpoint in room)
+        if rec.comm is not None:
+            where = self._sharded_where(where, si, rec)
+        elif where.layout == _Picks.HOST:                    # decided on the host: the picks as region ids (label_selected uploads them)
+            where.items = np.asarray(unl.b, np.int64)[si]
+        self._collected, self._last_sel = rec, where
+        self._selected = _Pairs(np.asarray(rec.rooms)[si], np.asarray(rec.spin)[si])      # (room id, superpoint in room)
         return sel, unl
 
-    def _sharded_where(self, where, si, unl, comm):
+    def _collect_device(self, rec):
+        """a one-call chain's d_result: counts, picks and the candidate list in one read-back"""
+        res = rec.buf.to_host(self.sel_stream)
+        if self.selector == "coregcn":
+            self.gcn_info = info = self.gcn_rows(info_only=True)
+            sampler.gcn_status_check(info, self.room_ids)
+        status = int(res[RES_STATUS])
+        if status & ~3:
+            raise RuntimeError("edcd_sampling: %s (status %d): nothing was selected" % (
+                "a cloud has more than 8192 candidates" if status & 4 else "the picks do not fit the capacities", status))
+        if status:
+            raise RuntimeError("gcn_fps_sampling: the candidate rule produced more rows than the capacities allow (status %d)" % status)
+        first = RES_HEADER + rec.max_select
+        cand = res[first: first + int(res[RES_N_UNL])].astype(np.int64)
+        rec.pairs = _Pairs(self.sp_cloud_h[cand], cand)      # (20 000 candidates in one AL round: the tuples are built when somebody reads them)
+        rec.rooms, rec.spin = self._room_sp(cand)
+        return res[RES_HEADER: RES_HEADER + int(res[RES_N_PICKS])].copy(), rec.pairs, _Picks(_Picks.RESULT0, rec.buf, rec.max_select)
+
+    def _collect_topk(self, rec):
+        """the top regions of the ranking (this rank's own): sel = arange"""
+        res = rec.buf.to_host(self.sel_stream)
+        loc = res[RES_HEADER: RES_HEADER + int(res[RES_N_UNL])].astype(np.int64)
+        rec.pairs = _Pairs(self.sp_cloud_h[loc], loc)
+        rec.rooms, rec.spin = self._room_sp(loc)
+        return np.arange(len(loc), dtype=np.int32), rec.pairs, _Picks(_Picks.RESULT1, rec.buf, rec.max_select)
+
+    def _collect_sharded(self, rec):
+        """the sharded device-side rule: the plan (counts, global candidate list) and the replicated picks"""
+        D = self.global_order; V = D["dev"]; rank = rec.comm.rank
+        plan = rec.buf.to_host(self.sel_stream)
+        sel = rec.picks.to_host(self.sel_stream)
+        if plan[RES_STATUS] or plan[PLAN_OVERFLOW]:
+            raise RuntimeError("gcn_fps_sharded: the candidate rule produced more rows than the capacities allow (status %d, %d)" % (
+                int(plan[RES_STATUS]), int(plan[PLAN_OVERFLOW])))
+        n_g, first = int(plan[PLAN_N_ALL]), _plan_gcand(rec.comm.world, V["nu_max"])
+        rec.gcand = gcand = plan[first: first + n_g].astype(np.int64)
+        loc = gcand[gcand // D["Smax"] == rank] - rank * D["Smax"]
+        rec.pairs = _Pairs(self.sp_cloud_h[loc], loc)
+        rec.rooms, rec.spin = D["room"][gcand], D["spin"][gcand]
+        rec.comb, rec.comb_n = V["d_glob"], n_g + (V["n_lab_all"] if self.selector == "kcenter" else 0)
+        if V["rep"] > 1:
+            rec.emu_mod = n_g
+        return sel, rec.pairs, _Picks(_Picks.REPLICATED, gcand=gcand)
+
+    def _collect_host(self, rec):
+        """decided on the host: the picks are a host array (the top of the host rule, a round without picks) or the chain's device array"""
+        sel = rec.picks if isinstance(rec.picks, np.ndarray) else rec.picks.to_host(self.sel_stream)
+        return sel, rec.pairs, _Picks(_Picks.HOST)
+
+    def _sharded_where(self, where, si, rec):
         """Where a sharded selection's picks lie, for label_selected(comm=).  fps / k-center: the picks and the global candidate list are replicated; a rank's
         items are the picks whose region it holds (`own`: their positions among all picks, which is also their place in self.selected).  edcd / topk: a
         rank holds its own picks only.  Host rule: the items and their 64-bit walk keys (cloud key << 32 | position in pick order) are made here."""
         D = self.global_order if self.global_order is not None else self._dist
-        Smax, rank = D["Smax"], comm.rank
+        Smax, rank, world = D["Smax"], rec.comm.rank, rec.comm.world
         if int(os.environ.get("SSDR_EMULATE_WORLD", "0")) > 1:
-            return dict(refuse="the selection ran under SSDR_EMULATE_WORLD (repeated rows: only its timing means anything)")
-        if isinstance(where, dict) and where["layout"] == "picks":          # device rule, fps / k-center
-            return dict(where, own=np.flatnonzero(where["gcand"][si] // Smax == rank))
-        if isinstance(where, dict):                                         # device rule, edcd / topk: the chain's own result buffer
-            return dict(where, own=np.arange(len(si)))
-        if self.selector in ("fps", "kcenter"):
-            gid = np.asarray(self._gcand_h, np.int64)[si]
+            return _Picks(_Picks.HOST, refuse="the selection ran under SSDR_EMULATE_WORLD (repeated rows: only its timing means anything)")
+        if where.layout == _Picks.REPLICATED:                               # device rule, fps / k-center
+            where.own = np.flatnonzero(where.gcand[si] // Smax == rank)
+        elif where.layout != _Picks.HOST:                                   # device rule, edcd / topk: the chain's own result buffer
+            where.own = np.arange(len(si))
+        elif self.selector in ("fps", "kcenter"):                           # host rule: the picks index the global candidate list
+            gid = np.asarray(rec.gcand, np.int64)[si]
             gc = D["gcloud"][gid]
-            first = np.full(comm.world * D["Bmax"], 1 << 30, np.int64)
+            first = np.full(world * D["Bmax"], 1 << 30, np.int64)
             np.minimum.at(first, gc, np.arange(len(gid)))                  # a cloud's first appearance among ALL picks
-            own = np.flatnonzero(gid // Smax == rank)
-            return dict(layout=None, items=gid[own] - rank * Smax, keys=(first[gc[own]] << 32) | own, own=own)
-        ids = np.asarray(unl.b if isinstance(unl, _Pairs) else [u[1] for u in unl], np.int64).reshape(-1)[si]
-        order = np.asarray(self._gorder_h, np.int64)                       # a cloud's first place in the global ranking among the regions that compete
-        r = np.flatnonzero(D["valid"][order])
-        key = np.full(comm.world * D["Bmax"], 0x7f7f7f7f, np.int64)
-        np.minimum.at(key, D["gcloud"][order[r]], r)
-        return dict(layout=None, items=ids, keys=(key[D["gcloud"][rank * Smax + ids]] << 32) | np.arange(len(ids)), own=np.arange(len(ids)))
+            where.own = own = np.flatnonzero(gid // Smax == rank)
+            where.items, where.keys = gid[own] - rank * Smax, (first[gc[own]] << 32) | own
+        else:                                                               # host rule, edcd / topk
+            ids = np.asarray(rec.pairs.b, np.int64)[si]
+            r = np.flatnonzero(D["valid"][rec.gorder])                      # a cloud's first place in the global ranking among the regions that compete
+            key = np.full(world * D["Bmax"], 0x7f7f7f7f, np.int64)
+            np.minimum.at(key, D["gcloud"][rec.gorder[r]], r)
+            where.items, where.keys, where.own = ids, (key[D["gcloud"][rank * Smax + ids]] << 32) | np.arange(len(ids)), np.arange(len(ids))
+        return where
 
     def gcn_rows(self, info_only=False):
         """what the last "coregcn" selection left on the device: (evaluation rows [rows,129] float64, trained parameters, (loss at step 0, loss after the
@@ -896,8 +937,7 @@ class HotPath:
         comm: the communicator of the last selection (a sharded round): every rank judges its own picks, the verdict records are all-gathered on the
         selection stream, every rank runs the same walk over all of them and applies its own.  The counters, budget_left and the class list are then
         global and equal on all ranks; `used` / `walk_pos` are this rank's used picks and their positions in the global walk."""
-        from . import sampler
-        last = getattr(self, "_last_comm", None)
+        last = None if self._collected is None else self._collected.comm
         if last is not None and comm is None:
             raise ValueError("label_selected: the last selection ran with a communicator; the budget walk is global over all ranks' picks: pass that "
                              "communicator (label_selected(comm=comm))")
@@ -905,28 +945,20 @@ class HotPath:
             if comm is not last:
                 raise ValueError("label_selected: comm must be the communicator of the last selection")
             return self._label_selected_sharded(comm, mode, threshold, min_size, budget)
-        where = getattr(self, "_last_sel", None)
-        if where is None:
-            raise RuntimeError("label_selected: no selection to label (run step_selection() / step() first)")
+        where, m, budget, min_size = self._label_begin(None, mode, budget, min_size)
         L, st, T = _lib.lib(), self.sel_stream, self._sel_static
-        m = sampler.label_mode([mode] if isinstance(mode, str) else mode)
-        batch = int(T["batch"])
-        budget = batch if budget is None else int(budget)
-        min_size = self.min_size if min_size is None else int(min_size)
-        if self.pseudo_mask is None:
-            self.set_pseudo_gt(np.zeros((2, self.n_pts), np.float32))
         edcd = self.selector == "edcd"
         d_key = DevArray((max(self.B, 1),), np.int32) if edcd else None
-        if where["layout"] is None:
-            items = where["items"]
+        if where.layout == _Picks.HOST:
+            items = where.items
             M = len(items)
             d_items = DevArray.from_host(np.concatenate([items, [0]]).astype(np.int32), st); d_n = DevArray.from_host(np.array([M], np.int32), st)
             if edcd:
                 _lib.check(L.ssdr_oracle_label_items_dev(None, 0, 0, self.sorted_inds.ptr, self.S, T["d_lab"].ptr, self.d_sp_cloud.ptr, self.B, None, 0, None, d_key.ptr, st))
         else:
-            M = int(where["max_select"])
+            M = where.max_select
             d_items = DevArray((max(M, 1),), np.int32); d_n = DevArray((1,), np.int32)
-            _lib.check(L.ssdr_oracle_label_items_dev(where["buf"].ptr, where["layout"], M, self.sorted_inds.ptr if edcd else None, self.S, T["d_lab"].ptr,
+            _lib.check(L.ssdr_oracle_label_items_dev(where.buf.ptr, where.layout, M, self.sorted_inds.ptr if edcd else None, self.S, T["d_lab"].ptr,
                                                      self.d_sp_cloud.ptr, self.B, d_items.ptr, M, d_n.ptr, d_key.ptr if edcd else None, st))
         nc = int(self.cfg.num_classes)
         cap = max(1, min(M * nc, max(budget, 0) + nc + 1))
@@ -944,8 +976,29 @@ class HotPath:
         n_items = int(d_n.to_host(st)[0])
         proc = proc[:n_items]
         upos = proc[used_f[proc] != 0]                       # the used picks in the order the walk met them
+        return self._label_end(out, d_cls, d_labeled, upos, np.flatnonzero(used_f[proc] != 0))
+
+    def _label_begin(self, comm, mode, budget, min_size):
+        """what both forms of label_selected start with: the picks' location, the mode, the click budget (default: the round's batch_size, one number for
+        all ranks of a sharded round), min_size, and pseudo labels to write into"""
+        where = self._last_sel
+        if where is None:
+            raise RuntimeError("label_selected: no selection to label (run step_selection(%s) / step(%s) first)" % (("", "") if comm is None else ("comm", "comm")))
+        if where.refuse:
+            raise ValueError("label_selected: " + where.refuse)
+        m = sampler.label_mode([mode] if isinstance(mode, str) else mode)
+        batch = int(self._sel_static["batch"] if comm is None else self._dist_setup(comm)["batch"])
+        if self.pseudo_mask is None:
+            self.set_pseudo_gt(np.zeros((2, self.n_pts), np.float32))
+        return where, m, batch if budget is None else int(budget), self.min_size if min_size is None else int(min_size)
+
+    def _label_end(self, out, d_cls, d_labeled, used_at, walk_pos):
+        """what both forms end with: the new entries of the class list (global, identical on every rank of a sharded round), the labelled set from the
+        device mask (set_labeled drops _dist: a sharded next round redoes the global draw), the picks spent, the LabelResult; used_at: the used picks'
+        places in self.selected, in the order the walk met them"""
+        st = self.sel_stream
         sel_pairs = self.__dict__.get("_selected")
-        used = _Pairs(np.asarray(sel_pairs.a)[upos], np.asarray(sel_pairs.b)[upos])
+        used = _Pairs(np.asarray(sel_pairs.a)[used_at], np.asarray(sel_pairs.b)[used_at])
         entries = d_cls.to_host(st)[: int(out[6])]
         self._class_list_h = np.concatenate([self._class_list_h, entries]).astype(np.int32)
         self.selected_class_list = DevArray.from_host(self._class_list_h)
@@ -953,44 +1006,32 @@ class HotPath:
         self.set_labeled({b: set(np.flatnonzero(mask & (self.sp_cloud_h == b)).tolist()) for b in range(self.B)})
         self._last_sel = None                                # (these picks are spent)
         return LabelResult(self, dict(zip(sampler.LABEL_COUNTERS, (int(x) for x in out[:6]))), int(out[7]), used, entries,
-                           dict(wave=int(out[10]), block=int(out[11])), np.flatnonzero(used_f[proc] != 0))
+                           dict(wave=int(out[10]), block=int(out[11])), walk_pos)
 
     def _label_selected_sharded(self, comm, mode, threshold, min_size, budget):
         """label_selected over a sharded round: walk keys -> verdict half -> all-gather of the records (the fourth exchange) -> walk half"""
-        from . import sampler
-        where = getattr(self, "_last_sel", None)
-        if where is None:
-            raise RuntimeError("label_selected: no selection to label (run step_selection(comm) / step(comm) first)")
-        if where.get("refuse"):
-            raise ValueError("label_selected: " + where["refuse"])
-        L, st, T = _lib.lib(), self.sel_stream, self._sel_static
+        where, m, budget, min_size = self._label_begin(comm, mode, budget, min_size)
+        L, st = _lib.lib(), self.sel_stream
         D = self._dist_setup(comm); V = D["dev"]
-        W, rank, Smax, Bmax = comm.world, comm.rank, D["Smax"], D["Bmax"]
-        m = sampler.label_mode([mode] if isinstance(mode, str) else mode)
-        batch = int(D["batch"])                               # the round's batch_size is one number for all ranks
-        budget = batch if budget is None else int(budget)
-        min_size = self.min_size if min_size is None else int(min_size)
-        if self.pseudo_mask is None:
-            self.set_pseudo_gt(np.zeros((2, self.n_pts), np.float32))
+        W, rank, Smax, Bmax, batch = comm.world, comm.rank, D["Smax"], D["Bmax"], int(D["batch"])
         # the record slots per rank: the most picks any rank can hold, from what _dist_setup exchanged
         # (fps / kcenter: the replicated chain may hand ALL picks to one rank, and the all-gather needs the same slot count on every rank)
         M = {"edcd": min(batch, int(D["nvalid_all"].max())), "topk": min(batch, Smax)}.get(self.selector, V["picks"])
         M = max(int(M), 1)
         d_items, d_n, d_keys = DevArray((M,), np.int32), DevArray((1,), np.int32), DevArray((M,), np.uint64)
-        if where["layout"] is None:                           # host rule: items and keys were made on the host
-            k = len(where["items"])
+        if where.layout == _Picks.HOST:                       # host rule: items and keys were made on the host
+            k = len(where.items)
             assert k <= M
-            _lib.check(L.ssdr_memcpy_h2d_on(d_items.ptr, _lib.ptr(np.ascontiguousarray(where["items"], np.int32)), 4 * k, st))
-            _lib.check(L.ssdr_memcpy_h2d_on(d_keys.ptr, _lib.ptr(np.ascontiguousarray(where["keys"]).astype(np.uint64)), 8 * k, st))
+            _lib.check(L.ssdr_memcpy_h2d_on(d_items.ptr, _lib.ptr(np.ascontiguousarray(where.items, np.int32)), 4 * k, st))
+            _lib.check(L.ssdr_memcpy_h2d_on(d_keys.ptr, _lib.ptr(np.ascontiguousarray(where.keys).astype(np.uint64)), 8 * k, st))
             _lib.check(L.ssdr_memcpy_h2d_on(d_n.ptr, _lib.ptr(np.array([k], np.int32)), 4, st))
-        elif where["layout"] == "picks":                      # the replicated picks over the replicated global candidate list
-            off = 16 + W + W * V["nu_max"]
-            _lib.check(L.ssdr_oracle_label_keys_dev(V["d_out"].ptr, V["picks"], V["d_plan"].ptr + 4 * 8, V["d_plan"].ptr + 4 * off, W * V["nu_max"], D["d_gcloud"].ptr, Smax,
-                                                    W * Bmax, rank, W, None, d_items.ptr, d_n.ptr, M, d_keys.ptr, st))
+        elif where.layout == _Picks.REPLICATED:               # the replicated picks over the replicated global candidate list
+            _lib.check(L.ssdr_oracle_label_keys_dev(V["d_out"].ptr, V["picks"], V["d_plan"].ptr + 4 * PLAN_N_ALL, V["d_plan"].ptr + 4 * _plan_gcand(W, V["nu_max"]),
+                                                    W * V["nu_max"], D["d_gcloud"].ptr, Smax, W * Bmax, rank, W, None, d_items.ptr, d_n.ptr, M, d_keys.ptr, st))
         else:                                                 # the rank's own picks; a cloud's key is its first place in the global ranking
             d_key = DevArray((W * Bmax,), np.int32)
-            ms = min(int(where["max_select"]), M)
-            _lib.check(L.ssdr_oracle_label_items_dev(where["buf"].ptr, where["layout"], int(where["max_select"]), D["d_ord"].ptr, W * Smax, V["d_glab"].ptr, D["d_gcloud"].ptr,
+            ms = min(where.max_select, M)
+            _lib.check(L.ssdr_oracle_label_items_dev(where.buf.ptr, where.layout, where.max_select, D["d_ord"].ptr, W * Smax, V["d_glab"].ptr, D["d_gcloud"].ptr,
                                                      W * Bmax, d_items.ptr, ms, d_n.ptr, d_key.ptr, st))
             _lib.check(L.ssdr_oracle_label_keys_dev(None, 0, None, None, 0, D["d_gcloud"].ptr, Smax, W * Bmax, rank, W, d_key.ptr, d_items.ptr, d_n.ptr, M, d_keys.ptr, st))
         nc = int(self.cfg.num_classes)
@@ -1011,21 +1052,12 @@ class HotPath:
         sampler.label_status_check(int(out[8]))
         n_items = int(d_n.to_host(st)[0])
         used_f, pos = d_used.to_host(st)[:n_items], d_pos.to_host(st)[:n_items]
-        own = np.asarray(where["own"], np.int64)
+        own = np.asarray(where.own, np.int64)
         if len(own) != n_items:
             raise RuntimeError("label_selected: the device found %d picks of this rank, the selection read back %d" % (n_items, len(own)))
         slots = np.flatnonzero(used_f != 0)
         slots = slots[np.argsort(pos[slots], kind="stable")]      # this rank's used picks in the order the global walk met them
-        sel_pairs = self.__dict__.get("_selected")
-        used = _Pairs(np.asarray(sel_pairs.a)[own[slots]], np.asarray(sel_pairs.b)[own[slots]])
-        entries = d_cls.to_host(st)[: int(out[6])]
-        self._class_list_h = np.concatenate([self._class_list_h, entries]).astype(np.int32)      # the global list, identical on every rank
-        self.selected_class_list = DevArray.from_host(self._class_list_h)
-        mask = d_labeled.to_host(st)[: self.S] != 0
-        self.set_labeled({b: set(np.flatnonzero(mask & (self.sp_cloud_h == b)).tolist()) for b in range(self.B)})      # (drops _dist: the next round redoes the global draw)
-        self._last_sel = None
-        return LabelResult(self, dict(zip(sampler.LABEL_COUNTERS, (int(x) for x in out[:6]))), int(out[7]), used, entries,
-                           dict(wave=int(out[10]), block=int(out[11])), pos[slots].astype(np.int64))
+        return self._label_end(out, d_cls, d_labeled, own[slots], pos[slots].astype(np.int64))
 
     def step(self, comm=None, timed_stages=False):
         """One pass of the hot path over the loaded batch of rooms.  Returns the selected candidate indices."""
@@ -1037,11 +1069,17 @@ class HotPath:
         self._front_end(); mark()
         self._pyramid(); mark()
         self._infer(); mark()
-        self._score(comm); mark()
+        self._score_async(comm); mark()
         out = self._select(comm); mark()
         if timed_stages:
             self.timing = dict(zip(("subsample+tile", "knn_pyramid", "randla_infer", "score", "select"), np.diff(t) * 1e3))
         return out
+
+
+def _new_stream():
+    st = C.c_void_p()
+    _lib.check(_lib.lib().ssdr_stream_create(C.byref(st)))
+    return st.value
 
 
 class LabelResult:
@@ -1114,21 +1152,14 @@ class ALRound:
         self.cfg, self.nb, self.B, self.rooms = config, len(self.batch_ids), len(rooms), rooms
         N = config.num_points
         self.tiles = self.nb * self.B
-        # five streams: front end and pyramid alternate between two streams each by the parity of the batch, so that a cross-stream wait ("everything
-        # the producer holds so far", ssdr_stream_wait) names exactly the batch it is meant for — with one stream per stage one of the three waits of a
-        # step always caught the neighbouring batch as well, and the stages overlapped two deep instead of three
         # One stream per stage.  A consumer stage waits for "everything its producer stream holds so far" (ssdr_stream_wait), which names exactly its own
         # batch because a step enqueues consumer first (inference k - 2, pyramid k - 1, front end k); the front end's wait for the LAST READER of the buffer
         # set it reuses (inference k - SLOTS) is an event recorded behind that inference (ssdr_event_*): with three buffer sets and a stream-wide wait the
         # front end ran at most two batches ahead and the 17 batches took 60 ms; five sets and the event: the stages run as far ahead as their inputs allow.
-        self.streams = []
-        for _ in range(3):
-            st = C.c_void_p(); _lib.check(L.ssdr_stream_create(C.byref(st))); self.streams.append(st.value)
+        self.streams = [_new_stream() for _ in range(3)]
         self.s_front, self.s_knn, self.s_inf = self.streams
         self.SLOTS = int(os.environ.get("SSDR_AL_SLOTS", self.SLOTS))
-        self.bstreams = []
-        for _ in range(self.SLOTS):
-            st = C.c_void_p(); _lib.check(L.ssdr_stream_create(C.byref(st))); self.bstreams.append(st.value)
+        self.bstreams = [_new_stream() for _ in range(self.SLOTS)]
         self.ev_inf = []
         for _ in range(self.nb):
             e = C.c_void_p(); _lib.check(L.ssdr_event_create(C.byref(e))); self.ev_inf.append(e.value)
@@ -1156,12 +1187,11 @@ class ALRound:
             self._bind(b)._front_end()
         _lib.sync(self.s_front)
         _lib.check(L.ssdr_grid_subsample_status(self.s_front, None))
-        from .synthetic import superpoints_from_tile
         tiles = self.xyz.to_host().reshape(self.tiles, N, 3)
         offs, pts, cloud, labeled = [np.zeros(1, np.int64)], [], [], {}
         tile_ids = [bg * self.B + i for bg in self.batch_ids for i in range(self.B)]      # global tile ids (a sharded round: this rank's)
         for t in range(self.tiles):
-            o, p = superpoints_from_tile(tiles[t])
+            o, p = synthetic.superpoints_from_tile(tiles[t])
             base = int(sum(len(x) for x in cloud))
             pts.append(p.astype(np.int64) + t * N); offs.append(o[1:].astype(np.int64) + offs[-1][-1]); cloud.append(np.full(len(o) - 1, t, np.int32))
             rng = np.random.default_rng([seed, tile_ids[t], 1])
@@ -1225,9 +1255,8 @@ class ALRound:
         self.sel._score_async(self.comm)
         self.sel._select_issue(self.comm)
         out = self.sel._select_collect()
-        from . import knn as _knn
         for st in [self.s_knn] + self.bstreams:
-            _knn.knn_status(st)
+            knn.knn_status(st)
             _lib.check(_lib.lib().ssdr_grid_subsample_status(st, None))
         _lib.check(_lib.lib().ssdr_grid_subsample_status(self.s_front, None))
         return out
@@ -1248,13 +1277,9 @@ class BatchStreams:
     def __init__(self, make_hot_path, slots=4, sel_streams=0):
         """sel_streams > 0: the selections run on that many streams of their own, taken in turn (a selection waits for its batch's stream; the batch's
         stream goes on to its next batch only after the host has read that selection: the buffer set is the same)"""
-        L = _lib.lib()
         self.depth = self.slots = int(slots)
-
-        def mkstream():
-            st = C.c_void_p(); _lib.check(L.ssdr_stream_create(C.byref(st))); return st.value
-        self.streams = [mkstream() for _ in range(self.slots)]
-        self.sel_streams = [mkstream() for _ in range(int(sel_streams))]
+        self.streams = [_new_stream() for _ in range(self.slots)]
+        self.sel_streams = [_new_stream() for _ in range(int(sel_streams))]
         self.hp = [make_hot_path() for _ in range(self.slots)]
         for h, st in zip(self.hp, self.streams):
             h.pipelined = True
@@ -1286,9 +1311,8 @@ class BatchStreams:
         _lib.sync()
         for st in self.streams + self.sel_streams:
             _lib.sync(st)
-        from . import knn as _knn
         for st in self.streams:
-            _knn.knn_status(st)
+            knn.knn_status(st)
             _lib.check(_lib.lib().ssdr_grid_subsample_status(st, None))
 
 
@@ -1300,7 +1324,6 @@ class _Prefix:
         self.__cuda_array_interface__ = {"shape": self.shape, "typestr": self.dtype.str, "data": (int(self.ptr), False), "version": 2, "strides": None}
 
     def host_view(self):
-        import ctypes as C
         return np.frombuffer((C.c_char * self.nbytes).from_address(int(self.ptr)), self.dtype)
 
 
@@ -1322,7 +1345,6 @@ class Pipelined:
         if groups is not None:
             depth = groups[-1] + 2
         assert groups is not None or depth in self.GROUPS
-        L = _lib.lib()
         self.depth = depth
         self.group = dict(zip(self.STAGES, groups if groups is not None else self.GROUPS[depth]))
         # The runtime spreads the streams over its (4) hardware queues in the order they are created, after the NULL stream and the
@@ -1330,10 +1352,6 @@ class Pipelined:
         # the overlap: measured on MI355X / ROCm 7.2 at depth 5 with one unused stream created in front of the stage streams 4.8 ms per
         # step, without it 6.4, with two 6.1, with three 5.3, with the unused one in any later position 5.7-6.2 (`GPU_MAX_HW_QUEUES=8`, every
         # stream on a queue of its own: 4.8 as well).  So: one spare in front.
-        def mkstream():
-            st = C.c_void_p()
-            _lib.check(L.ssdr_stream_create(C.byref(st)))
-            return st.value
         qmap = os.environ.get("SSDR_PIPE_QMAP")              # development: "f,k,i,s,a,b" = the hardware queue (1..GPU_MAX_HW_QUEUES) wanted for the front / knn / infer /
         if qmap and depth == 5 and overlap_select:           # score streams and the two selection streams ("-" for a: the library stream, queue 1)
             # ROCm 7.2's runtime (read off rocprofv3's queue ids, tools/gpu_qdiscover.sh): the library's stream holds queue 1, the NULL stream queue 2, every new stream
@@ -1354,32 +1372,29 @@ class Pipelined:
                 for _ in range(64):
                     nq = next_queue()
                     refs[nq] = refs.get(nq, 0) + 1
-                    st = mkstream()
+                    st = _new_stream()
                     if nq == q:
                         return st
                     self._spares.append(st)
                 raise RuntimeError("SSDR_PIPE_QMAP: queue %d not reachable" % q)
-            order = sorted(range(6), key=lambda i: 0)      # creation in the order given: front, knn, infer, score, selA, selB
-            made = {}
-            for i in order:
-                made[i] = None if want[i] == "-" else on_queue(want[i])
-            self.streams = [made[0], made[1], made[2], made[3]]
-            self.sel_streams = [made[4], made[5]]
+            made = []                                       # creation in the order given: front, knn, infer, score, selA, selB
+            for i in range(6):
+                made.append(None if want[i] == "-" else on_queue(want[i]))
+            self.streams, self.sel_streams = made[:4], made[4:]
             self._spare = None
         else:
-            self._spare = mkstream()
-            self.streams = [mkstream() for _ in range(depth - 1)]
+            self._spare = _new_stream()
+            self.streams = [_new_stream() for _ in range(depth - 1)]
             self.sel_streams = [None]                        # selections alternate between the library stream and one of their own
             if overlap_select:
-                self.sel_streams.append(mkstream())
+                self.sel_streams.append(_new_stream())
         self.overlap_select = overlap_select
         # sel_lag: how many selections behind the newest the host waits for (1: the previous batch's).  The sharded run's replicated global FPS
         # grows with the square of the rank count: from 4 ranks on a chain is longer than two steps, and sel_lag = 2 keeps
         # three chains in flight on three streams, with one more buffer set so that no stage overwrites what a running selection reads
         self.sel_lag = max(1, int(sel_lag)) if overlap_select else 1
         for _ in range(self.sel_lag - 1):
-            self.sel_streams.append(mkstream())
-        self._uncollected = None
+            self.sel_streams.append(_new_stream())
         self._issued = []                                    # selections enqueued, not collected yet (oldest first)
         self.lead = {n: depth - 1 - g for n, g in self.group.items()}      # batches ahead of the selection
         # one buffer set per batch in flight (a spare set, so that no stage has to wait for the previous selection's buffers, was
@@ -1425,7 +1440,7 @@ class Pipelined:
         k0 = self._k if steady else 0
         last = None if steady else steps                     # batches >= last are never issued
         if k0 == 0:
-            self._uncollected = None; self._issued = []
+            self._issued = []
             for b in range(first if steady else min(steps, first)):      # prologue: fill the pipe
                 for name in self.STAGES:
                     if b < lead[name]:
@@ -1449,7 +1464,6 @@ class Pipelined:
                 self._issued.append(k)
                 while len(self._issued) > self.sel_lag:
                     out = self.hp[self._issued.pop(0) % self.slots]._select_collect()
-                self._uncollected = self._issued[0] if self._issued else None
                 for name, b in deferred:
                     self._stage(name, b)
             else:
@@ -1459,21 +1473,17 @@ class Pipelined:
             if out is None and self._issued:                       # a short call right after the fill: nothing older to hand back
                 while self._issued:
                     out = self.hp[self._issued.pop(0) % self.slots]._select_collect()
-                self._uncollected = None
         else:
             while self.overlap_select and self._issued:
                 out = self.hp[self._issued.pop(0) % self.slots]._select_collect()
-            self._uncollected = None
             self._drain()
         return out
 
     def finish(self):
         """end a steady run: wait for everything issued and forget the partially processed batches"""
-        while getattr(self, "_issued", None):
+        while self._issued:
             self.hp[self._issued.pop(0) % self.slots]._select_collect()
-        self._uncollected = None
         self._drain()
-        from . import knn as _knn
-        _knn.knn_status(self.streams[self.group["knn"]])     # everything has finished: the blocking checks
+        knn.knn_status(self.streams[self.group["knn"]])     # everything has finished: the blocking checks
         _lib.check(_lib.lib().ssdr_grid_subsample_status(self.streams[self.group["front"]], None))
         self._k = 0

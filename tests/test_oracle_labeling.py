@@ -300,23 +300,28 @@ def _check_label(hp, res, exp, labelled_before):
     return labelled
 
 
-@pytest.mark.parametrize("selector,host_rule", [("fps", False), ("kcenter", False), ("edcd", False), ("topk", False), ("fps", True), ("edcd", True)])
+@pytest.mark.parametrize("selector,host_rule", [("fps", False), ("kcenter", False), ("edcd", False), ("topk", False),
+                                                ("fps", True), ("kcenter", True), ("edcd", True), ("topk", True)])
 def test_round_label_and_next_round(backend, selector, host_rule, monkeypatch):
-    """the picks of each selector (device rule: from the chain's result buffer; host rule: uploaded), labelled, and the next round on the updated state"""
+    """the picks of each selector (device rule: from the chain's result buffer; host rule: uploaded), labelled, and the next round on the updated state:
+    it selects what the oracle does and what a fresh HotPath over the labelled sets and the class list the first round ended with does"""
     from ssdr_al import pipeline
     if host_rule:
         monkeypatch.setenv("SSDR_SELECT_HOST_RULE", "1")
     clouds, labelled, sel_list = make_clouds(31, 4, 36, 3, 40, labelled_per_cloud=6)
     batch, min_size = 24, 5
-    hp = pipeline.HotPath.from_clouds(clouds, labelled, sel_list, _cfg(), sampler_args=EDCD_ARGS if selector == "edcd" else FPS_ARGS, selector=selector,
-                                      min_size=min_size, batch_size=batch, round_num=2, label_seed=0)
+    kw = dict(sampler_args=EDCD_ARGS if selector == "edcd" else FPS_ARGS, selector=selector, min_size=min_size, batch_size=batch, round_num=2, label_seed=0)
+    hp = pipeline.HotPath.from_clouds(clouds, labelled, sel_list, _cfg(), **kw)
     class_list = sel_list.tolist()
     for rnd in range(2):
-        hp.step_selection()
+        sel, unl = hp.step_selection()
         assert hp.rule_path == ("host" if host_rule else "device")
         picks, cloud_order = _oracle_picks(clouds, labelled, np.asarray(class_list), selector, batch, min_size)
         assert hp.selected == picks                          # (round 2: the hand-over — labelled set, skip mask, class list — is the oracle's)
-        if rnd == 1:
+        if rnd == 1:          # nothing of the first selection is left on the object
+            fresh = pipeline.HotPath.from_clouds(clouds, labelled, np.asarray(class_list), _cfg(), **kw)
+            fsel, funl = fresh.step_selection()
+            assert np.array_equal(fsel, sel) and funl == unl and fresh.selected == hp.selected
             break
         oc = _oracle_clouds(hp)
         exp = O.label_round(picks, oc, [np.zeros((2, len(c["gt"])), np.float32) for c in oc], "NAIL", 0.6, batch - 5, min_size, class_list, cloud_order)
@@ -398,7 +403,7 @@ def test_refusals(backend):
     clouds, labelled, sel_list = make_clouds(2, 2, 12, 3, 20, labelled_per_cloud=2)
     hp = pipeline.HotPath.from_clouds(clouds, labelled, sel_list, _cfg(), selector="topk", batch_size=4)
     hp.step_selection()
-    hp._last_comm = object()
+    hp._collected.comm = object()
     with pytest.raises(ValueError, match="communicator"):
         hp.label_selected()
 

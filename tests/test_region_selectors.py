@@ -301,6 +301,27 @@ def test_topk_round_is_the_ranking_head(backend, batch, monkeypatch):
     assert hp.rule_path == "host" and unl_h == unl and np.array_equal(sel_h, sel) and hp.selected == exp
 
 
+# ---- 4b. the host route of fps / k-center: what the device routes hand over -----------------------------------------------------------------------------
+@pytest.mark.parametrize("selector", ["fps", "kcenter"])
+def test_round_without_picks_selects_nothing(backend, selector):
+    """batch_size 0: the device rule hands the round to the host route, which returns an empty selection and an empty candidate list"""
+    from ssdr_al import pipeline
+    clouds, labelled, sel_list = _s3dis_clouds()
+    hp = pipeline.HotPath.from_clouds(clouds, labelled, sel_list, _cfg(), selector=selector, batch_size=0)
+    sel, unl = hp.step_selection()
+    assert hp.rule_path == "host"
+    assert len(sel) == 0 and unl == [] and hp.selected == []
+
+
+def test_kcenter_without_a_labelled_region_is_refused(backend):
+    """k-center seeds its chain with the labelled rows: with none in any cloud the host route's kCenterGreedy call refuses the round"""
+    from ssdr_al import _lib, pipeline
+    clouds, labelled, sel_list = _s3dis_clouds()
+    hp = pipeline.HotPath.from_clouds(clouds, [set() for _ in clouds], sel_list, _cfg(), selector="kcenter", batch_size=30)
+    with pytest.raises(_lib.SsdrError, match="already_selected"):
+        hp.step_selection()
+
+
 def test_selector_for_follows_the_reference_branch_order():
     from ssdr_al import pipeline
     assert pipeline.selector_for(["sb", "WetSU", "clsbal", "edcd"]) == "edcd"
