@@ -175,21 +175,26 @@ int ssdr_split3_dev(const float* d_xyz, size_t n, size_t max_size, size_t recurs
  * to center[3] (host), order them by the caller's shuffle d_perm (a permutation of [0,num_points)), subtract the
  * centre, and emit d_out_xyz [num_points,3], d_out_feat [num_points,3+color_dim] = [xyz_centred, colors*scale]
  * (may be NULL) and d_out_idx [num_points] = source row (may be NULL).  A cloud with fewer than num_points rows
- * is padded by duplicating row floor(d_dup_u[r] * m) of the shuffled list (d_dup_u: uniform [0,1) floats). */
+ * is padded by duplicating row floor(d_dup_u[r] * m) of the shuffled list (d_dup_u: uniform [0,1) floats).
+ * An empty cloud (*d_m <= 0) has no row to take or to duplicate: the call reads none of its points or colours and
+ * leaves d_out_xyz / d_out_feat / d_out_idx as they were. */
 int ssdr_tile_select_dev(const float* d_points, const float* d_colors, int color_dim, const int64_t* d_m, size_t n_max,
                          const float* center, size_t num_points, const int32_t* d_perm, const float* d_dup_u, float color_scale,
                          float* d_out_xyz, float* d_out_feat, int32_t* d_out_idx, void* stream);
 
 /* Batch form: cloud r = rows [cloud_offsets[r], cloud_offsets[r+1]) with live count d_m[r]; centers host [num_clouds,3];
  * d_perm / d_dup_u [num_clouds, num_points]; outputs [num_clouds, num_points, ...].  d_out_idx = source row inside its cloud.
- * d_labels (int32, one per row, may be NULL) -> d_out_labels [num_clouds, num_points] = queried_pc_label (s3dis_dataset.py:141). */
+ * d_labels (int32, one per row, may be NULL) -> d_out_labels [num_clouds, num_points] = queried_pc_label (s3dis_dataset.py:141).
+ * An empty cloud (d_m[r] <= 0: what ssdr_grid_subsample_batch_dev hands on for a cloud it refused, status bit 2) has no row to take or to
+ * duplicate: none of its points, colours or labels is read, and its rows of every output stay as they were; the other clouds are not affected. */
 int ssdr_tile_select_batch_dev(const float* d_points, const float* d_colors, int color_dim, const int64_t* d_m, const int64_t* cloud_offsets,
                                size_t num_clouds, const float* centers, size_t num_points, const int32_t* d_perm, const float* d_dup_u,
                                float color_scale, float* d_out_xyz, float* d_out_feat, int32_t* d_out_idx, const int32_t* d_labels,
                                int32_t* d_out_labels, void* stream);
 /* Test-time variant (S3/s3dis_dataset_test.py:105-143): the same tile, plus the possibility-map update
  * possibility[idx] += (1 - dists/max(dists))^2 over the tile's (un-padded) points (float64 map, float32 dists) and,
- * optionally, min / argmin of the updated map (the next pick: :106-108). */
+ * optionally, min / argmin of the updated map (the next pick: :106-108).  An empty cloud (*d_m <= 0): the tile outputs and the
+ * map stay as they were; the minimum over no rows comes out as 1e300 with arg-min 0x7fffffff. */
 int ssdr_tile_select_possibility_dev(const float* d_points, const float* d_colors, int color_dim, const int64_t* d_m, size_t n_max,
                                      const float* center, size_t num_points, const int32_t* d_perm, const float* d_dup_u, float color_scale,
                                      float* d_out_xyz, float* d_out_feat, int32_t* d_out_idx,

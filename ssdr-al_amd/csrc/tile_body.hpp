@@ -41,6 +41,7 @@ __device__ __forceinline__ void tile_gather_body(const float* __restrict__ pts, 
                                                    const int* __restrict__ labels = nullptr, int* out_lab = nullptr) {
     const int m = *d_count;
     const int avail = min(m, num_points);
+    if (avail <= 0) return;                                // an empty cloud has no row to take or to duplicate (`sorted` holds nothing of this call): its output rows stay as they were
     for (int r = (bx < 0 ? (int)blockIdx.x : bx) * 256 + threadIdx.x; r < num_points; r += gridDim.x * 256) {
         int pos;
         if (avail == num_points) pos = perm[r];
