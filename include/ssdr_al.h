@@ -671,6 +671,65 @@ int ssdr_feed_augment_dev(const float* d_xyz, size_t num_tiles, size_t num_point
 int ssdr_feed_prefix_dev(const float* d_xyz, size_t num_tiles, size_t num_points, size_t num_sub, float* d_out, void* stream);
 int ssdr_feed_status(void* stream, int32_t* out_status);
 
+/* ---- RandLA-Net training (csrc/randla_train.hip; SSDR_AL_s3dis/RandLANet.py:36-84, :140-180, :486-585, helper_tf_util.py:111-246) ----
+ * One handle holds the raw, unfolded network: per unit W, b, gamma, beta, the moving mean and variance, Adam's m and v.  float32 throughout.
+ * Units in graph order: fc0 | per encoder level mlp1, LFAmlp1, LFAatt_pooling_1fc, LFAatt_pooling_1mlp, LFAmlp2, LFAatt_pooling_2fc,
+ * LFAatt_pooling_2mlp, mlp2, shortcut | decoder_0 | Decoder_layer_0 .. L-1 | fc1, fc2, fc.
+ * Parameter tensors, for each unit in that order: W, b (if the unit has a bias), gamma, beta, moving mean, moving variance (if it has a batch norm).
+ *   ssdr_randla_train_param_shape: unit, kind (0 W, 1 b, 2 gamma, 3 beta, 4 moving mean, 5 moving variance), rows x cols as stored: W is
+ *   [in, out], the Decoder_layer_j kernels (conv2d_transpose) [out, in]; vectors are [1, out].
+ *   ssdr_randla_train_set_param / _get_param: host pointers, synchronous.  which = 0 the tensor, 1 Adam's m, 2 Adam's v (kinds 0..3 only).
+ *   ssdr_randla_train_get_grad: the gradient the last step / grads call left (kinds 0..3).  _set_grad and _apply_dev (one Adam update from the
+ *   gradients as they stand) exist for tests of the optimiser.
+ * ssdr_randla_train_set_loss: class_weights f32 [num_classes] (NULL: ones); ignored_labels: labels dropped from the loss, the remaining labels
+ *   shifted down as reducing_list does (:66-71), so labels run over 0 .. num_classes + n_ignored - 1.
+ * The *_dev calls only enqueue on `stream`; the host reads no device value.  d_xyz / d_neigh / d_pool / d_interp: host arrays of num_layers
+ *   device pointers: xyz_l f32 [B, N_l, 3], neigh_l i32 [B, N_l, 16], pool_l i32 [B, N_l+1, 16], interp_l i32 [B, N_l, 1] (tf_map's input_list);
+ *   d_features f32 [B, N, in_dim], d_labels i32 [B N], d_activation / d_pseudo f32 [B N], d_drop_mask u8 [B N, 32] (1 = kept, scaled by 2).
+ *   d_loss / d_accuracy (device f32, may be NULL) receive get_loss's mean over the valid rows and mean(argmax == label).
+ *   _step_dev: forward (batch statistics, dropout), loss, backward, the moving statistics (momentum 0.99) and Adam as tf.train.AdamOptimizer
+ *     (lr_t = lr sqrt(1 - b2^t) / (1 - b1^t), p -= lr_t m / (sqrt(v) + 1e-8)).
+ *   _grads_dev: forward and backward only: weights, moving statistics and the step count stay.
+ *   _forward_dev: d_logits f32 [B N, num_classes] and d_feat32 f32 [B N, 32] (fc2's output before the dropout).  is_training = 0 normalises with the
+ *     moving statistics and ignores the mask (may be NULL).
+ *   The backward pass scatters with float atomicAdd: gradients and updated weights differ in their low bits from run to run; forward values do not.
+ * ssdr_randla_train_export: folds the batch norms with the moving statistics and loads an inference handle of the same configuration
+ *   (ssdr_randla_set_layer's table, mlp2 and shortcut stacked).  Synchronous.
+ * ssdr_randla_train_workspace_bytes: activation + gradient workspace of the last (B, N) laid out.  ssdr_randla_train_last_ms: waits for the handle's
+ *   last call; milliseconds of its forward, loss + backward and update parts (HIP events on its stream).
+ * ssdr_randla_train_dropout_mask_dev: d_mask u8 [n] from a counter-based hash of (seed, step, index).
+ * ssdr_randla_train_status: waits for `stream`; bit 0 = a loss without a valid row (loss and gradients are 0), bit 1 = a label or pseudo label outside
+ *   the table (its row is dropped).  Clears the bits; SSDR_ERR_INVALID when one was set.
+ * Refused before anything is launched: k_n != 16 (SSDR_ERR_UNSUPPORTED); NULL arguments, unset parameters, a level whose rows are not divisible by
+ *   its ratio (SSDR_ERR_INVALID). */
+int ssdr_randla_train_create(int num_layers, const int32_t* d_out, int k_n, int num_classes, int in_dim, void** handle);
+void ssdr_randla_train_destroy(void* handle);
+int ssdr_randla_train_num_params(void* handle);
+int ssdr_randla_train_param_shape(void* handle, int i, int* unit, int* kind, int* rows, int* cols);
+int ssdr_randla_train_set_param(void* handle, int i, int which, const float* host);
+int ssdr_randla_train_get_param(void* handle, int i, int which, float* host);
+int ssdr_randla_train_get_grad(void* handle, int i, float* host);
+int ssdr_randla_train_set_grad(void* handle, int i, const float* host);
+int ssdr_randla_train_apply_dev(void* handle, void* stream);
+int ssdr_randla_train_set_loss(void* handle, const float* class_weights, const int32_t* ignored_labels, int n_ignored);
+int ssdr_randla_train_set_lr(void* handle, float lr);
+int ssdr_randla_train_set_step_count(void* handle, int64_t t);
+int64_t ssdr_randla_train_step_count(void* handle);
+size_t ssdr_randla_train_workspace_bytes(void* handle);
+int ssdr_randla_train_last_ms(void* handle, float* out3);
+int ssdr_randla_train_dropout_mask_dev(uint64_t seed, uint64_t step, size_t n, uint8_t* d_mask, void* stream);
+int ssdr_randla_train_step_dev(void* handle, size_t B, size_t N, const float* d_features, const float* const* d_xyz, const int32_t* ratios,
+                               const int32_t* const* d_neigh, const int32_t* const* d_pool, const int32_t* const* d_interp, const int32_t* d_labels,
+                               const float* d_activation, const float* d_pseudo, const uint8_t* d_drop_mask, float* d_loss, float* d_accuracy, void* stream);
+int ssdr_randla_train_grads_dev(void* handle, size_t B, size_t N, const float* d_features, const float* const* d_xyz, const int32_t* ratios,
+                                const int32_t* const* d_neigh, const int32_t* const* d_pool, const int32_t* const* d_interp, const int32_t* d_labels,
+                                const float* d_activation, const float* d_pseudo, const uint8_t* d_drop_mask, float* d_loss, float* d_accuracy, void* stream);
+int ssdr_randla_train_forward_dev(void* handle, size_t B, size_t N, const float* d_features, const float* const* d_xyz, const int32_t* ratios,
+                                  const int32_t* const* d_neigh, const int32_t* const* d_pool, const int32_t* const* d_interp, const uint8_t* d_drop_mask,
+                                  int is_training, float* d_logits, float* d_feat32, void* stream);
+int ssdr_randla_train_export(void* handle, void* net);
+int ssdr_randla_train_status(void* stream, int32_t* out_status);
+
 /* ---- plain device memory for callers without their own allocator (tests, the ctypes mirror) ---------- */
 int ssdr_dev_alloc(size_t bytes, void** d_ptr);
 int ssdr_dev_free(void* d_ptr);

@@ -19,6 +19,9 @@ class ConfigS3DIS:                      # helper_tool.py:46-75 (the fields the h
     d_out = [16, 64, 128, 256, 512]
     noise_init = 3.5
     train_steps = 500                   # :27 (training.TrainFeeder: one_epoch_steps)
+    max_epoch = 30                      # :63-68 (trainer.Trainer: train_round, decay)
+    learning_rate = 1e-2
+    lr_decays = {i: 0.84 for i in range(0, 500)}
 
 
 class ConfigSemantic3D:                 # helper_tool.py:77-117
@@ -34,6 +37,9 @@ class ConfigSemantic3D:                 # helper_tool.py:77-117
     d_out = [16, 64, 128, 256, 512]
     noise_init = 3.5
     train_steps = 667                   # SSRD_AL_semantic3d/helper_tool.py:57: batches per epoch of get_batch
+    max_epoch = 50                      # :99-102 (trainer.Trainer)
+    learning_rate = 1e-2
+    lr_decays = {i: 0.9 for i in range(0, 500)}
     augment_scale_anisotropic = True    # :81-88, read by tf_augment_input (training.TrainFeeder)
     augment_symmetries = [True, False, False]
     augment_rotation = 'vertical'

@@ -8,7 +8,7 @@ Semantic3D: Semantic3D_Dataset_Train.get_batch (the reference's SSRD_AL_semantic
 Both:       tf_map's pyramid (ssdr_knn_pyramid_dev with the pool outputs) on the generator's stream, the sub-sampled xyz levels copied out as the
             prefixes they are (ssdr_feed_prefix_dev).
 
-The training step itself (forward, loss, backward, optimiser) stays in the caller's framework."""
+The training step itself (forward, loss, backward, optimiser) is ``trainer.Trainer.step``."""
 import ctypes as C
 
 import numpy as np
