@@ -16,7 +16,7 @@ from ssdr_al import _lib  # noqa: E402
 _lib.use(os.path.join(ROOT, "ssdr-al_amd", "libssdr_al.so"))
 L = _lib.lib()
 rng = np.random.default_rng(2)
-shapes = [(20000, 32, 300), (9472, 32, 400), (6000, 16, 60)]      # fps_coop_reg (counter form, 40 workgroups), fps_coop_tag (19), fps_coop
+shapes = [(20000, 32, 300), (9472, 32, 400), (6000, 16, 60)]      # coop_split<2> (79 workgroups), coop_split<2> (37), coop
 streams, feats, outs = [], [], []
 for n, D, count in shapes:
     st = C.c_void_p(); _lib.check(L.ssdr_stream_create(C.byref(st))); streams.append(st.value)

@@ -1,5 +1,5 @@
-"""Worker of tests/test_fps_paths.py::test_environment_selected_forms: a process of its own because the switches that select a form of the FPS / k-center
-chain (SSDR_FPS_COOP_SWEEP, SSDR_FPS_COOP_COUNTER, SSDR_KC_TILED, SSDR_FPS_SLOT_SHIFT) are read once per process.  Arguments: "n:na" sizes (D = 32).  For
+"""Worker of tests/test_fps_paths.py::test_environment_selected_forms: a process of its own because the switches that shape the FPS / k-center chain
+(SSDR_KC_TILED, SSDR_FPS_SLOT_SHIFT) are read once per process.  Arguments: "n:na" sizes (D = 32).  For
 every size four legs through the C ABI on the gfx950 build — FPS and k-center, over standard-normal rows and over every row twice at shuffled positions —
 each printed as "LEG n leg rc status minus match gap_ok forms": entry return code, ssdr_select_status word, picks of -1, picks == oracle (index for
 index), input condition met, and the fps_form / fps_seed scopes the profiler reported."""

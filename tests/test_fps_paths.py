@@ -1,6 +1,6 @@
 """Farthest-point sampling and k-center greedy, launcher branch by launcher branch, against the float64 oracle (oracle/select_np.py).
 
-fps_like() (csrc/select_fps.hip) picks one of eleven kernels and one of three seedings from (D, n, seeded, environment); a wrong pick still returns
+fps_like() (csrc/select_fps.hip) picks one of eight kernels and one of three seedings from (D, n, seeded, environment); a wrong pick still returns
 `count` plausible indices.  It names what it took in two zero-work profiler scopes inside "fps_chain" ("fps_form:*", "fps_seed:*").  Every case here
 runs through the C ABI (ssdr_fps_dev: squared distances; ssdr_kcenter_dev: their square roots, seeded by kc_init / kc_init_tiled), must equal
 oracle.select_np.farthest_features_sample / kcenter_greedy INDEX FOR INDEX, must leave ssdr_select_status at 0 with no pick of -1, and must report
@@ -17,14 +17,14 @@ block<0>; above -> step (one launch per pick).  Its leg runs every case with n <
 checks the form that build must take; "fps_form:block<32>" is reached there only (on the GPU it needs the occupancy query to refuse the cooperative
 grid, which no test may force).
 
-The environment-selected forms (SSDR_FPS_COOP_SWEEP = 0 / 1 / 2 / 3 / 5 / 6, SSDR_FPS_COOP_COUNTER, SSDR_KC_TILED, SSDR_FPS_SLOT_SHIFT) are read once
-per process: tests/_fps_forms_worker.py runs them in one child process per environment, one after another.
+No environment switch selects a form.  The two that change what a form does (SSDR_KC_TILED = 0: kc_init at every size; SSDR_FPS_SLOT_SHIFT: the size of
+a coop_split record's slot) are read once per process: tests/_fps_forms_worker.py runs them in one child process per environment, one after another.
 
 The live row count below the capacity (`d_n`) is reached through ssdr_fps_gathered_dev / ssdr_kcenter_gathered_dev, whose compacted array the caller
 owns: rows beyond the live count hold 1e30, which would win every arg-max if a kernel read them.
 
-Measured on one MI355X: `pytest -m gpu tests/test_fps_paths.py` = 117 tests in 48 s wall, most of it the NumPy oracle.  Slowest: the eleven child
-processes 1.4 - 3.8 s each (kc_tiled0 3.8 s), rest_coop_far 2.1 s, n262144 1.3 s, d129_n70001 1.2 s; the one-launch-per-pick cases: n2pow20 (2^20 + 7 rows
+Measured on one MI355X: `pytest -m gpu tests/test_fps_paths.py` = 109 tests in 28 s wall, most of it the NumPy oracle.  Slowest: the three child
+processes under 1 s to 3.9 s each (kc_tiled0 3.9 s), rest_coop_far 2.1 s, n262144 1.3 s, d129_n70001 1.2 s; the one-launch-per-pick cases: n2pow20 (2^20 + 7 rows
 x 8 picks) 1.1 s, n262145 (30 picks) 1.0 s, ties_step 1.0 s, kc_step 0.8 s.  The CPU logic build's leg (`-m "not gpu"`, 88 tests): about 50 s on 16
 threads.  Smallest arg-max gap met over all cases: 4.3e-7 (n5003).
 """
@@ -310,30 +310,22 @@ def test_live_count_below_capacity(backend, selector, cap, live, n_lab, form, em
         assert np.array_equal(got, exp), (selector, cap, live, data, got, exp)
 
 
-# ---- the environment-selected forms, one child process per environment ----------------------------------------------------------------------
-SWEEP_M = {1: "coop_sweep_m1", 2: "coop_sweep_m2", 3: "coop_sweep_m3"}
-# (id, environment, [(n, na of the seeded leg, form, seeding of the seeded leg)]); D = 32 throughout.  G = ceil(n / 512) for the unsplit forms.
+# ---- the environment switches, one child process per environment ----------------------------------------------------------------------------
+# (id, environment, [(n, na of the seeded leg, form, seeding of the seeded leg)]); D = 32 throughout.
 ENV_ROWS = [
-    ("sweep0", {"SSDR_FPS_COOP_SWEEP": "0"}, [(2368, 100, "coop_tag", "kc_init"), (20000, 100, "coop_reg", "kc_init")]),
-    ("sweep0_counter1", {"SSDR_FPS_COOP_SWEEP": "0", "SSDR_FPS_COOP_COUNTER": "1"}, [(2368, 100, "coop_reg", "kc_init"), (20000, 100, "coop_reg", "kc_init")]),
-    ("sweep0_counter0", {"SSDR_FPS_COOP_SWEEP": "0", "SSDR_FPS_COOP_COUNTER": "0"}, [(2368, 100, "coop_tag", "kc_init"), (20000, 100, "coop_tag", "kc_init")]),
-    *[("sweep%d" % m, {"SSDR_FPS_COOP_SWEEP": str(m)}, [(4736, 100, SWEEP_M[m], "kc_init"), (20000, 100, SWEEP_M[m], "kc_init"), (40000, 100, "coop_reg", "kc_init")])
-      for m in (1, 2, 3)],
-    ("sweep5", {"SSDR_FPS_COOP_SWEEP": "5"}, [(4736, 100, "coop_split<4>", "kc_init"), (32768, 100, "coop_split<4>", "kc_init"), (32769, 100, "coop_reg", "kc_init")]),
-    ("sweep6", {"SSDR_FPS_COOP_SWEEP": "6"}, [(4736, 100, "coop_wave", "kc_init"), (32768, 100, "coop_wave", "kc_init"), (32769, 100, "coop_reg", "kc_init")]),
     ("kc_tiled0", {"SSDR_KC_TILED": "0"}, [(24000, 4000, "coop_split<2>", "kc_init")]),
     ("slot_shift4", {"SSDR_FPS_SLOT_SHIFT": "4"}, [(4736, 100, "coop_split<2>", "kc_init")]),
     ("slot_shift7", {"SSDR_FPS_SLOT_SHIFT": "7"}, [(4736, 100, "coop_split<2>", "kc_init")]),
 ]
-ENV_NAMES = ("SSDR_FPS_COOP_SWEEP", "SSDR_FPS_COOP_COUNTER", "SSDR_KC_TILED", "SSDR_FPS_SLOT_SHIFT", "SSDR_FPS_COOP_G", "SSDR_FPS_COOP_BUDGET", "SSDR_FPS_DELAY", "SSDR_FPS_DBG")
+ENV_NAMES = ("SSDR_KC_TILED", "SSDR_FPS_SLOT_SHIFT", "SSDR_FPS_COOP_G", "SSDR_FPS_COOP_BUDGET", "SSDR_FPS_DELAY", "SSDR_FPS_DBG")
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,env_add,sizes", ENV_ROWS, ids=[r[0] for r in ENV_ROWS])
 def test_environment_selected_forms(name, env_add, sizes):
-    """Every form an environment switch selects, in a child process of its own (the switches are read once per process; never two GPU children at a
-    time): for every size FPS and k-center, each over standard-normal rows and over every row twice, index for index the oracle's sequence, status 0,
-    and the form / seeding the dispatch must have taken under that environment (above a form's own limit: the form it falls through to)."""
+    """Every environment switch that changes what a chain does, in a child process of its own (the switches are read once per process; never two GPU
+    children at a time): for every size FPS and k-center, each over standard-normal rows and over every row twice, index for index the oracle's sequence,
+    status 0, and the form / seeding the dispatch must have taken under that environment."""
     _gpu_lib()
     env = {k: v for k, v in os.environ.items() if k not in ENV_NAMES}
     env.update(env_add)
@@ -367,7 +359,8 @@ def test_cases_cover_every_form_and_seeding():
     may force; it counts as covered by the CPU logic build's cases (every D = 32 case of 1537 .. 16 384 rows takes it there)."""
     src = open(os.path.join(ROOT, "ssdr-al_amd", "csrc", "select_fps.hip")).read()
     names = set(re.findall(r'"(fps_(?:form|seed):[^"]+)"', src))
-    assert len(names) >= 17, sorted(names)
+    assert names == {"fps_form:block_reg<1>", "fps_form:block_reg<2>", "fps_form:block_reg<3>", "fps_form:block<0>", "fps_form:block<32>", "fps_form:step", "fps_form:coop",
+                     "fps_form:coop_split<2>", "fps_seed:fill", "fps_seed:kc_init", "fps_seed:kc_init_tiled"}, sorted(names)
     gpu = {r for c in CASES for r in c.reach} | {"fps_form:" + form for _, _, sizes in ENV_ROWS for _, _, form, _ in sizes} | \
           {"fps_seed:" + seed for _, _, sizes in ENV_ROWS for _, _, _, seed in sizes}
     emu = {_emu_form(c.n, c.D) for c in CASES if c.emu}

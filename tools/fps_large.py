@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """FPS at the reference's real scale (ssdr_main_S3DIS2.py:134: 10 000 picks over ~2 x 10^4 candidate regions, 32-d features):
    python tools/fps_large.py [n] [count] [--oracle] [--save f.npy] [--cmp f.npy]
-   -> time of ssdr_fps_dev (the form is the library's choice, or SSDR_FPS_COOP_SWEEP / SSDR_FPS_COOP_COUNTER), and the index sequence against the
-   NumPy oracle (--oracle) or against a sequence an earlier run saved (--cmp)"""
+   -> time of ssdr_fps_dev (the form is the library's choice; SSDR_AL_LIBRARY selects another build of the library for an A/B run), and the index
+   sequence against the NumPy oracle (--oracle) or against a sequence an earlier run saved (--cmp)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "ssdr-al_amd"))
@@ -25,8 +25,7 @@ for rep in range(3):
     _lib.sync(); dt = time.perf_counter() - t0
     best = min(best, dt)
 st = _lib.lib().ssdr_select_status(None, None)
-print("ssdr_fps_dev n=%d count=%d form=%s/%s: %.2f ms (%.3f us per pick) status=%d" % (n, count, os.environ.get("SSDR_FPS_COOP_SWEEP", "-"), os.environ.get("SSDR_FPS_COOP_COUNTER", "-"),
-                                                                                best * 1e3, best * 1e6 / count, st), flush=True)
+print("ssdr_fps_dev n=%d count=%d: %.2f ms (%.3f us per pick) status=%d" % (n, count, best * 1e3, best * 1e6 / count, st), flush=True)
 got = d_o.to_host()
 if opt("--save"):
     np.save(opt("--save"), got)
