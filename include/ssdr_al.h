@@ -692,10 +692,16 @@ int ssdr_feed_status(void* stream, int32_t* out_status);
  *   _grads_dev: forward and backward only: weights, moving statistics and the step count stay.
  *   _forward_dev: d_logits f32 [B N, num_classes] and d_feat32 f32 [B N, 32] (fc2's output before the dropout).  is_training = 0 normalises with the
  *     moving statistics and ignores the mask (may be NULL).
- *   The backward pass scatters with float atomicAdd: gradients and updated weights differ in their low bits from run to run; forward values do not.
+ *   By default the backward pass scatters with float atomicAdd: gradients and updated weights differ in their low bits from run to run; forward
+ *   values do not.
+ * ssdr_randla_train_set_deterministic(handle, on): on != 0 replaces the three backward scatters (gather_neighbour, nearest_interpolation,
+ *   random_sample) with reductions over inverse lists built from the call's own index arrays (csrc/scatter_det.hip): every source row adds its
+ *   positions in ascending order, no float atomic, so gradients and weights are the same bits every run.  Off is the default and launches the
+ *   atomic kernels.  Changing it plans the workspace again at the next call; ssdr_randla_train_deterministic reads the switch back.
  * ssdr_randla_train_export: folds the batch norms with the moving statistics and loads an inference handle of the same configuration
  *   (ssdr_randla_set_layer's table, mlp2 and shortcut stacked).  Synchronous.
- * ssdr_randla_train_workspace_bytes: activation + gradient workspace of the last (B, N) laid out.  ssdr_randla_train_last_ms: waits for the handle's
+ * ssdr_randla_train_workspace_bytes: activation + gradient workspace of the last (B, N) laid out, in deterministic mode plus the lists, their
+ *   sort scratch and the pooling shares.  ssdr_randla_train_last_ms: waits for the handle's
  *   last call; milliseconds of its forward, loss + backward and update parts (HIP events on its stream).
  * ssdr_randla_train_dropout_mask_dev: d_mask u8 [n] from a counter-based hash of (seed, step, index).
  * ssdr_randla_train_status: waits for `stream`; bit 0 = a loss without a valid row (loss and gradients are 0), bit 1 = a label or pseudo label outside
@@ -729,6 +735,21 @@ int ssdr_randla_train_forward_dev(void* handle, size_t B, size_t N, const float*
                                   int is_training, float* d_logits, float* d_feat32, void* stream);
 int ssdr_randla_train_export(void* handle, void* net);
 int ssdr_randla_train_status(void* stream, int32_t* out_status);
+int ssdr_randla_train_set_deterministic(void* handle, int on);
+int ssdr_randla_train_deterministic(void* handle);
+
+/* The two atomic-free reductions of the deterministic mode as stand-alone pieces (csrc/scatter_det.hip); scratch per stream, enqueue only.
+ * ssdr_scatter_add_rows_dev: d_idx i32 [B, rows_per_b] into src_rows rows per batch element, clamped to [0, src_rows - 1];
+ *   dsrc[(b, idx[b, r]), c] += dout[(b, r), c] for c < C, where every source row first sums its positions in ascending r from +0 in float32 and
+ *   then adds that sum to its old value; a row no position points at is not written.  ldo / lds: leading dimensions of dout / dsrc.
+ * ssdr_pool_grad_rows_dev: the backward of the max over 16 pooled rows.  d_idx i32 [B, m_per_b, 16]; src / dsrc [B src_rows, C] (lds), out / dout
+ *   [B m_per_b, C] (ldo).  Position r = m * 16 + k is tied when src[(b, idx[b, m, k]), c] == out[m, c]; a tied position contributes
+ *   dout[m, c] / (float)ties(m, c), summed per source row in ascending r as above.
+ * Refused (SSDR_ERR_INVALID): NULL pointers, C <= 0, a leading dimension below C.  B * rows_per_b == 0 is a no-op. */
+int ssdr_scatter_add_rows_dev(const int32_t* d_idx, int B, int rows_per_b, int src_rows, const float* d_dout, int ldo, int C, float* d_dsrc, int lds,
+                              void* stream);
+int ssdr_pool_grad_rows_dev(const float* d_src, float* d_dsrc, int lds, int src_rows, const int32_t* d_idx, int B, int m_per_b, int C,
+                            const float* d_out, const float* d_dout, int ldo, void* stream);
 
 /* ---- plain device memory for callers without their own allocator (tests, the ctypes mirror) ---------- */
 int ssdr_dev_alloc(size_t bytes, void** d_ptr);

@@ -316,6 +316,11 @@ __global__ __launch_bounds__(RS_BS) void rs_finish(SortPtrs s) {
 
 }  // namespace
 
+size_t RadixSorter::scratch_bytes(size_t slots) {
+    const size_t nb = (slots + RS_TILE - 1) / RS_TILE + 1;
+    return (8 * slots + 16) + (4 * slots + 16) + (4 * 256 * nb + 4 * 256 * (size_t)RADIX_MAX_SEG) + 16 * RADIX_MAX_SEG * (size_t)(RS_ANDOR_G + 1);
+}
+
 int RadixSorter::reserve(size_t slots) {
     nblocks_max = (int)((slots + RS_TILE - 1) / RS_TILE) + 1;
     SSDR_TRY(k1.reserve(8 * slots + 16)); SSDR_TRY(v1.reserve(4 * slots + 16));

@@ -13,9 +13,11 @@
 // Inference layer `l` of csrc/randla_model.hip is unit l for fc0, units 1 + 9 i + (0..6) for 1 + 8 i + (0..6), units 1 + 9 i + 7 and + 8 stacked
 // for 1 + 8 i + 7, and unit l + L from decoder_0 on.
 //
-// The scatter-adds behind gather_neighbour, nearest_interpolation and random_sample use float atomicAdd: the low bits of the gradients (and of the
-// weights after a step) depend on the run.  Forward values do not.
+// The scatter-adds behind gather_neighbour, nearest_interpolation and random_sample use float atomicAdd by default: the low bits of the gradients (and
+// of the weights after a step) depend on the run.  Forward values do not.  ssdr_randla_train_set_deterministic(handle, 1) replaces the three scatters
+// with reductions over inverse lists (scatter_det.hip) that add in a fixed order: then the gradients and the weights are the same bits every run.
 #include "ssdr_internal.hpp"
+#include "scatter_det.hpp"
 #include <cmath>
 #include <cstring>
 #include <functional>
@@ -441,6 +443,17 @@ struct Train {
     LossTables tb{};
     float lr = 0.01f; long step = 0;
     bool params_set = false;
+    // deterministic mode: the inverse lists of neigh / pool / interp of every level (list 3 i + 0 / 1 / 2), laid out by det_layout
+    struct DetList { long off_at, pos_at; int src_rows, rows_per_b; };
+    bool det = false, planned_det = false;
+    std::vector<DetList> dl; std::vector<int> levels;      // levels: N_0 .. N_L of the last shape planned
+    long list_ints = 0, key_slots = 0, share_floats = 0;
+    DevBuf lists; RadixSorter sorter;                       // lists: [off and pos of every list | sort keys u64 [key_slots] | pooling shares f32 [share_floats]]
+    InvList list(int i) const { return InvList{lists.as<int>() + dl[i].off_at, lists.as<int>() + dl[i].pos_at}; }
+    uint64_t* sort_keys() const { return reinterpret_cast<uint64_t*>(lists.as<int>() + list_ints); }
+    float* shares() const { return reinterpret_cast<float*>(sort_keys() + key_slots); }
+    size_t det_bytes() const { return (size_t)list_ints * 4 + (size_t)key_slots * 8 + (size_t)share_floats * 4 + RadixSorter::scratch_bytes(sort_slots()); }
+    size_t sort_slots() const { return ((size_t)key_slots + RADIX_TILE - 1) / RADIX_TILE * RADIX_TILE; }       // RadixSorter::sort rounds up to whole tiles
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};     // start, forward done, backward done, update done of the last call (ssdr_randla_train_last_ms)
     bool ev_valid = false;
     ~Train() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
@@ -616,10 +629,12 @@ struct Runner {
         return SSDR_OK;
     }
     // y[(b, r), :] = src[(b, idx[b, r]), :]
-    int gather(const View& src, int src_rows, const int32_t* idx, int rows_per_b, int B, const View& y) {
-        const long total = (long)B * rows_per_b; const int Cw = src.w;
+    // list: which of the handle's inverse lists belongs to idx (deterministic mode)
+    int gather(const View& src, int src_rows, const int32_t* idx, int rows_per_b, int B, const View& y, int list) {
+        const long total = (long)B * rows_per_b; const int Cw = src.w; const bool det = m.det;
         if (!dry) { hipLaunchKernelGGL(gather_rows_kernel, dim3(blocks_for(total * Cw)), dim3(256), 0, s, src.v, src.ld, src_rows, idx, rows_per_b, total, Cw, y.v, y.ld); SSDR_HIP(hipGetLastError()); }
         push([=]() -> int {
+            if (det) return scatter_rows_det(m.list(list), B, rows_per_b, src_rows, y.g, y.ld, Cw, src.g, src.ld, s);
             hipLaunchKernelGGL(scatter_rows_kernel, dim3(blocks_for(total * Cw)), dim3(256), 0, s, src.g, src.ld, src_rows, idx, rows_per_b, total, Cw, y.g, y.ld);
             SSDR_HIP(hipGetLastError()); return SSDR_OK;
         });
@@ -636,10 +651,11 @@ struct Runner {
         });
         return SSDR_OK;
     }
-    int pool(const View& src, int src_rows, const int32_t* idx, int m_per_b, int B, const View& y) {
-        const long total = (long)B * m_per_b; const int Cw = src.w;
+    int pool(const View& src, int src_rows, const int32_t* idx, int m_per_b, int B, const View& y, int list) {
+        const long total = (long)B * m_per_b; const int Cw = src.w; const bool det = m.det;
         if (!dry) { hipLaunchKernelGGL(pool_fwd_kernel, dim3(blocks_for(total * Cw)), dim3(256), 0, s, src.v, src.ld, src_rows, idx, m_per_b, total, Cw, y.v, y.ld); SSDR_HIP(hipGetLastError()); }
         push([=]() -> int {
+            if (det) return pool_grad_det(m.list(list), src.v, src.g, src.ld, src_rows, idx, B, m_per_b, Cw, y.v, y.g, y.ld, m.shares(), s);
             hipLaunchKernelGGL(pool_bwd_kernel, dim3(blocks_for(total * Cw)), dim3(256), 0, s, src.v, src.g, src.ld, src_rows, idx, m_per_b, total, Cw, y.v, y.g, y.ld);
             SSDR_HIP(hipGetLastError()); return SSDR_OK;
         });
@@ -660,12 +676,12 @@ struct Runner {
             View rel = alloc(R, 10, false);
             if (!dry) { hipLaunchKernelGGL(relpos_kernel, dim3(blocks_for(R)), dim3(256), 0, s, d_xyz[i], d_neigh[i], n, R, rel.v); SSDR_HIP(hipGetLastError()); }
             View fcat1 = alloc(R, d, true);
-            SSDR_TRY(gather(f_pc, n, d_neigh[i], n * 16, B, cols(fcat1, 0, h)));
+            SSDR_TRY(gather(f_pc, n, d_neigh[i], n * 16, B, cols(fcat1, 0, h), 3 * i));
             SSDR_TRY(conv(base + 1, rel, (int)R, cols(fcat1, h, h)));
             View agg1 = alloc(rows, d, true); SSDR_TRY(attention(base + 2, fcat1, rows, agg1));
             View a1 = alloc(rows, h, true); SSDR_TRY(conv(base + 3, agg1, rows, a1));
             View fcat2 = alloc(R, d, true);
-            SSDR_TRY(gather(a1, n, d_neigh[i], n * 16, B, cols(fcat2, 0, h)));
+            SSDR_TRY(gather(a1, n, d_neigh[i], n * 16, B, cols(fcat2, 0, h), 3 * i));
             SSDR_TRY(conv(base + 4, cols(fcat1, h, h), (int)R, cols(fcat2, h, h)));
             View agg2 = alloc(rows, d, true); SSDR_TRY(attention(base + 5, fcat2, rows, agg2));
             View a2 = alloc(rows, d, true); SSDR_TRY(conv(base + 6, agg2, rows, a2));
@@ -677,7 +693,7 @@ struct Runner {
             View samp;
             if (i <= L - 2) { samp = cols(alloc(rows_next, 2 * d + 2 * m.d_out[i + 1], true), 0, 2 * d); }
             else samp = alloc(rows_next, 2 * d, true);
-            SSDR_TRY(pool(out, n, d_pool[i], N[i + 1], B, samp));
+            SSDR_TRY(pool(out, n, d_pool[i], N[i + 1], B, samp, 3 * i + 1));
             if (i == 0) enc.push_back(out);
             enc.push_back(samp);
             f = samp;
@@ -690,7 +706,7 @@ struct Runner {
             const int e = (int)enc.size() - j - 2; const View skip = enc[e]; const int n = enc_n[e];
             if (skip.ld != skip.w + feat.w) { set_error("randla_train: decoder %d: skip buffer laid out for %d interpolated channels, got %d", j, skip.ld - skip.w, feat.w); return SSDR_ERR_INTERNAL; }
             View cat = skip; cat.w = skip.ld;
-            SSDR_TRY(gather(feat, feat_n, d_interp[L - 1 - j], n, B, cols(cat, skip.w, feat.w)));       // nearest_interpolation :550-559
+            SSDR_TRY(gather(feat, feat_n, d_interp[L - 1 - j], n, B, cols(cat, skip.w, feat.w), 3 * (L - 1 - j) + 2));       // nearest_interpolation :550-559
             View y = alloc(B * n, skip.w, true); SSDR_TRY(conv(ui++, cat, B * n, y));
             feat = y; feat_n = n;
         }
@@ -734,8 +750,29 @@ int check_common(Train* m, const StepIn& in, std::vector<int>& N, const char* wh
     return SSDR_OK;
 }
 
+// Deterministic mode's share of the workspace for B tiles of N[0] points: list 3 i is neigh_i (the level's two gathers share it), 3 i + 1 pool_i,
+// 3 i + 2 interp_i; one key buffer for the largest list and one share buffer for the largest pooling follow.  Sizes only, nothing is allocated.
+void det_layout(Train* m, long B, const std::vector<int>& N) {
+    m->dl.clear(); m->list_ints = m->key_slots = m->share_floats = 0;
+    auto add = [&](int src_rows, long rows_per_b) {
+        Train::DetList d{m->list_ints, m->list_ints + inv_off_ints(B, src_rows), src_rows, (int)rows_per_b};
+        m->list_ints = d.pos_at + inv_pos_ints(B, rows_per_b);
+        m->key_slots = std::max(m->key_slots, B * rows_per_b);
+        m->dl.push_back(d);
+    };
+    for (int i = 0; i < m->L; ++i) {
+        add(N[i], (long)N[i] * 16); add(N[i], (long)N[i + 1] * 16); add(N[i + 1], N[i]);
+        m->share_floats = std::max(m->share_floats, B * N[i + 1] * 2L * m->d_out[i]);
+    }
+}
+
 int plan(Train* m, const StepIn& in, const std::vector<int>& N, hipStream_t s) {
-    if (m->planned_B == in.B && m->planned_N == in.N) return SSDR_OK;
+    if (m->planned_B == in.B && m->planned_N == in.N && m->planned_det == m->det && m->levels == N) return SSDR_OK;
+    if (m->det) {
+        det_layout(m, (long)in.B, N);
+        SSDR_TRY(m->lists.reserve((size_t)m->list_ints * 4 + (size_t)m->key_slots * 8 + (size_t)m->share_floats * 4));
+        SSDR_TRY(m->sorter.reserve(m->sort_slots()));
+    }
     Runner dryrun{*m, s, true, true, false, true};
     View a, b;
     SSDR_TRY(dryrun.forward((int)in.B, N, in.d_features, in.d_xyz, in.d_neigh, in.d_pool, in.d_interp, nullptr, &a, &b));
@@ -745,6 +782,7 @@ int plan(Train* m, const StepIn& in, const std::vector<int>& N, hipStream_t s) {
     const long rows0 = (long)in.B * in.N;
     SSDR_TRY(m->lpart.reserve((size_t)(rows0 * 8 + (rows0 / 256 + 2) * 12 + 64)));
     m->act_floats = dryrun.a_off; m->grad_floats = dryrun.g_off; m->planned_B = in.B; m->planned_N = in.N;
+    m->planned_det = m->det; m->levels = N;
     return SSDR_OK;
 }
 
@@ -776,6 +814,16 @@ int run(Train* m, const StepIn& in, int is_training, int mode, float* d_logits, 
     hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, s, lp, nb, m->fin.as<float>(), d_loss, d_acc, status);
     hipLaunchKernelGGL(loss_grad_kernel, dim3(blocks_for(rows0)), dim3(256), 0, s, logits.v, m->C, rows0, row_w, row_cls, m->fin.as<float>(), logits.g);
     SSDR_HIP(hipGetLastError());
+    // the lists are built from the index arrays of THIS call, every call: a feeder hands out the same buffers with new contents
+    if (m->det) {
+        for (int i = 0; i < m->L; ++i) {
+            const int32_t* const idx[3] = {in.d_neigh[i], in.d_pool[i], in.d_interp[i]};
+            for (int k = 0; k < 3; ++k) {
+                const Train::DetList& d = m->dl[3 * i + k];
+                SSDR_TRY(inv_list_build(idx[k], (int)in.B, d.rows_per_b, d.src_rows, m->sort_keys(), m->list(3 * i + k), m->sorter, s));
+            }
+        }
+    }
     for (size_t i = r.tape.size(); i-- > 0;) SSDR_TRY(r.tape[i]());
     SSDR_HIP(hipEventRecord(m->ev[2], s));
     if (mode & 2) {
@@ -928,7 +976,21 @@ int ssdr_randla_train_set_step_count(void* handle, int64_t t) {
 }
 int64_t ssdr_randla_train_step_count(void* handle) { return handle ? (int64_t)static_cast<Train*>(handle)->step : -1; }
 /* bytes of the activation + gradient workspaces laid out by the last call */
-size_t ssdr_randla_train_workspace_bytes(void* handle) { Train* m = static_cast<Train*>(handle); return m ? (size_t)(m->act_floats + m->grad_floats) * 4 : 0; }
+size_t ssdr_randla_train_workspace_bytes(void* handle) {
+    Train* m = static_cast<Train*>(handle);
+    return m ? (size_t)(m->act_floats + m->grad_floats) * 4 + (m->det && !m->dl.empty() ? m->det_bytes() : 0) : 0;
+}
+
+/* on != 0: the three backward scatters become reductions over inverse lists (scatter_det.hip), the same bits every run.  Off (the default) launches
+ * the atomic kernels.  The workspace is planned again at the next call; when a shape has been planned already its new size is reported at once. */
+int ssdr_randla_train_set_deterministic(void* handle, int on) {
+    Train* m = static_cast<Train*>(handle);
+    if (!m) { set_error("randla_train_set_deterministic: bad handle"); return SSDR_ERR_INVALID; }
+    m->det = on != 0;
+    if (m->det && !m->levels.empty()) det_layout(m, (long)m->planned_B, m->levels);
+    return SSDR_OK;
+}
+int ssdr_randla_train_deterministic(void* handle) { return handle ? (static_cast<Train*>(handle)->det ? 1 : 0) : 0; }
 
 /* Waits for the last forward / grads / step call of this handle; out3 = milliseconds of its forward, loss + backward and update parts (HIP events). */
 int ssdr_randla_train_last_ms(void* handle, float* out3) {
@@ -947,8 +1009,8 @@ int ssdr_randla_train_dropout_mask_dev(uint64_t seed, uint64_t step, size_t n, u
     return SSDR_OK;
 }
 
-/* Forward, loss, backward, the moving statistics and one Adam update; enqueue only.  The scatter-adds are float atomics: the weights' low bits depend
- * on the run. */
+/* Forward, loss, backward, the moving statistics and one Adam update; enqueue only.  By default the scatter-adds are float atomics and the weights' low
+ * bits depend on the run; not so after ssdr_randla_train_set_deterministic(handle, 1). */
 int ssdr_randla_train_step_dev(void* handle, size_t B, size_t N, const float* d_features, const float* const* d_xyz, const int32_t* ratios,
                                const int32_t* const* d_neigh, const int32_t* const* d_pool, const int32_t* const* d_interp, const int32_t* d_labels,
                                const float* d_activation, const float* d_pseudo, const uint8_t* d_drop_mask, float* d_loss, float* d_accuracy, void* stream) {

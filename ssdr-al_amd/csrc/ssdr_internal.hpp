@@ -109,6 +109,7 @@ struct RadixSorter {
     int nblocks_max = 0;
     bool wide_high = false;      // keys whose bits above 32 vary (a ranking by float value): wide passes up there too when the set is large, not the one-workgroup kernel
     int reserve(size_t slots);
+    static size_t scratch_bytes(size_t slots);      // what reserve(slots) asks of the device
     // key_bits: upper bound on the significant key bits when the caller knows one (skips launching higher passes)
     // input_in_alt: the caller wrote the unsorted pairs into alt_keys() / alt_vals() (valid after reserve()) instead of keys / vals;
     // with an odd number of executed digit passes the result then lands in keys / vals without the final copy

@@ -3,8 +3,9 @@
 weighted cross entropy on the pseudo labels, the backward pass and tf.train.AdamOptimizer's update in libssdr_al.so (csrc/randla_train.hip).
 
 Weights travel as the reference-named dict that ``randlanet.Network.load`` takes (entries ``W``, ``b``, ``bn = (gamma, beta, mean, var)``,
-``transposed``), raw and unfolded.  The scatter-adds of the backward pass are float atomics: gradients and updated weights differ in their low
-bits from run to run, forward values (logits, loss, accuracy of given weights) do not."""
+``transposed``), raw and unfolded.  By default the scatter-adds of the backward pass are float atomics: gradients and updated weights differ in
+their low bits from run to run, forward values (logits, loss, accuracy of given weights) do not.  ``Trainer(..., deterministic=True)`` (or
+``set_deterministic``) replaces them with reductions in a fixed order: the same inputs then give the same bits every run."""
 import ctypes as C
 
 import numpy as np
@@ -46,6 +47,8 @@ def _bind(L):
     L.ssdr_randla_train_forward_dev.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     L.ssdr_randla_train_export.argtypes = [vp, vp]
     L.ssdr_randla_train_status.argtypes = [vp, C.POINTER(i32)]
+    L.ssdr_randla_train_set_deterministic.argtypes = [vp, i32]
+    L.ssdr_randla_train_deterministic.argtypes = [vp]
     L._train_bound = True
     return L
 
@@ -54,7 +57,7 @@ class Trainer:
     """``Trainer(config).load(weights)``, then ``step(batch)`` per ``TrainFeeder`` batch, ``loss()`` / ``accuracy()`` when a number is wanted and
     ``export_to(network)`` for ``infer``, ``VoteTester`` or ``WholeCloudPredictor``.  ``train_round(feeder, epochs, tester)`` is ``Network.train``."""
 
-    def __init__(self, config=ConfigS3DIS, in_dim=6, class_weights=None, ignored_labels=(), lr=None, seed=0):
+    def __init__(self, config=ConfigS3DIS, in_dim=6, class_weights=None, ignored_labels=(), lr=None, seed=0, deterministic=False):
         self.config, self.in_dim, self.seed = config, int(in_dim), int(seed)
         self.L, self.Cn = int(config.num_layers), int(config.num_classes)
         self._h = C.c_void_p()
@@ -82,6 +85,8 @@ class Trainer:
         self._loss, self._acc = DevArray((1,), np.float32), DevArray((1,), np.float32)
         self._mask = None
         self._last_stream = None
+        if deterministic:
+            self.set_deterministic(True)
 
     def __del__(self):
         try:
@@ -176,6 +181,16 @@ class Trainer:
     def decay(self, epoch):
         """learning_rate *= config.lr_decays[epoch] (RandLANet.py:258-260)"""
         return self.set_lr(self.lr * float(self.config.lr_decays[epoch]))
+
+    def set_deterministic(self, flag):
+        """True: the backward scatters add in a fixed order (no float atomics), gradients and weights are reproducible bit for bit; takes effect
+        at the next call, which plans the (larger) workspace again.  False (the default): the atomic kernels."""
+        _lib.check(self._lib.ssdr_randla_train_set_deterministic(self._h, 1 if flag else 0))
+        return self
+
+    @property
+    def deterministic(self):
+        return bool(self._lib.ssdr_randla_train_deterministic(self._h))
 
     def workspace_bytes(self):
         return int(self._lib.ssdr_randla_train_workspace_bytes(self._h))

@@ -6,10 +6,13 @@ Without arguments the tool is a driver: it starts itself twice as a child proces
      (ssdr_randla_train_last_ms), the step time from a host clock around steps that end in a stream synchronise;
   2. `--child trace` under `rocprofv3 --kernel-trace --stats` (a run of its own: tracing slows the host), from whose kernel statistics the ten
      slowest kernels are listed;
-and prints one JSON line.  The FLOP count is computed from the shapes (every dense layer: 2 M in out forward, the same again for dW and for dX
+and prints one JSON line.  With --deterministic the timed child measures the step in BOTH modes in the same process (the default atomic scatters
+first, then Trainer.set_deterministic(True) on the same trainer and batch: forward / backward / update for each, and the workspace), and the traced
+child runs in deterministic mode: from the per-dispatch kernel trace of its last step comes the share of the step's kernel time that the list
+builds (key generation, the radix sort, the offsets) and the two reductions take.  The FLOP count is computed from the shapes (every dense layer: 2 M in out forward, the same again for dW and for dX
 where the input has a gradient; the attention softmax and the other element-wise work are not counted) and set against the float32 vector and
 matrix peaks of the MI355X, which are the same 157.3 TFLOP/s.
-Usage: python tools/train_probe.py [--rooms 8] [--steps 5] [--warmup 2] [--points 40960] [--batch 6] [--out bench_out/train_probe]"""
+Usage: python tools/train_probe.py [--deterministic] [--rooms 8] [--steps 5] [--warmup 2] [--points 40960] [--batch 6] [--out bench_out/train_probe]"""
 import argparse
 import csv
 import glob
@@ -74,27 +77,41 @@ def child(mode, a):
     assert batch.size == cfg.batch_size, "need at least batch_size rooms"
     arrays = batch.arrays                       # the same batch every step: the step's time does not depend on the values
     steps = a.steps if mode == "time" else 1
-    for _ in range(a.warmup):
-        tr.step_arrays(arrays)
-    _lib.sync()
-    split, wall = [], []
-    for _ in range(steps):
-        t0 = time.perf_counter()
-        tr.step_arrays(arrays)
+    med = lambda v: float(np.median(v))
+
+    def timed():
+        for _ in range(a.warmup):
+            tr.step_arrays(arrays)
         _lib.sync()
-        wall.append(1e3 * (time.perf_counter() - t0))
-        split.append(tr.last_ms())
+        split, wall = [], []
+        for _ in range(steps):
+            t0 = time.perf_counter()
+            tr.step_arrays(arrays)
+            _lib.sync()
+            wall.append(1e3 * (time.perf_counter() - t0))
+            split.append(tr.last_ms())
+        return split, wall
+    if a.deterministic and mode == "trace":
+        tr.set_deterministic(True)
+    split, wall = timed()
+    det = None
+    if a.deterministic and mode == "time":           # the same trainer, the same batch, the other mode
+        ws_default = tr.workspace_bytes()
+        tr.set_deterministic(True)
+        dsplit, dwall = timed()
+        det = dict(step_ms_events=round(med([sum(s) for s in dsplit]), 3), step_ms_host=round(med(dwall), 3),
+                   forward_ms=round(med([s[0] for s in dsplit]), 3), backward_ms=round(med([s[1] for s in dsplit]), 3), update_ms=round(med([s[2] for s in dsplit]), 3),
+                   workspace_gib=round(tr.workspace_bytes() / 2.0 ** 30, 3), workspace_growth_mib=round((tr.workspace_bytes() - ws_default) / 2.0 ** 20, 1))
     loss = tr.loss()
     assert np.isfinite(loss) and tr.status() == 0
     fwd, bwd = dense_flops(cfg, cfg.batch_size, tr.specs)
-    med = lambda v: float(np.median(v))
     step_ms = med([sum(s) for s in split])
-    out = dict(mode=mode, B=cfg.batch_size, N=cfg.num_points, steps=steps, warmup=a.warmup, loss=loss,
+    out = dict(mode=mode, deterministic=bool(tr.deterministic) if det is None else None, deterministic_mode=det, B=cfg.batch_size, N=cfg.num_points, steps=steps, warmup=a.warmup, loss=loss,
                step_ms_events=round(step_ms, 3), step_ms_host=round(med(wall), 3),
                forward_ms=round(med([s[0] for s in split]), 3), backward_ms=round(med([s[1] for s in split]), 3), update_ms=round(med([s[2] for s in split]), 3),
                dense_gflop=dict(forward=round(fwd / 1e9, 2), backward=round(bwd / 1e9, 2)),
                tflops=round((fwd + bwd) / (step_ms * 1e-3) / 1e12, 3), share_of_f32_peak=round((fwd + bwd) / (step_ms * 1e-3) / PEAK_F32, 4),
-               workspace_gib=round(tr.workspace_bytes() / 2.0 ** 30, 3))
+               workspace_gib=round((tr.workspace_bytes() if det is None else ws_default) / 2.0 ** 30, 3))
     batch.release(None)
     feeder.close()
     print("TRAIN_PROBE " + json.dumps(out))
@@ -113,6 +130,30 @@ def slowest_kernels(out_dir, n=10):
     return rows[:n]
 
 
+LIST_KERNELS = ("inv_keys_kernel", "inv_off_kernel", "::rs_")                       # the list builds: keys, the radix sort's kernels, offsets
+REDUCE_KERNELS = ("rows_reduce_kernel", "pool_share_kernel", "pool_reduce_kernel")  # the two reductions
+
+
+def deterministic_share(out_dir):
+    """share of the LAST step's kernel time (per-dispatch kernel trace; a step ends with its adam_kernel dispatch) spent in the list builds and in
+    the two reductions"""
+    files = glob.glob(os.path.join(out_dir, "**", "*kernel_trace.csv"), recursive=True)
+    if not files:
+        return None
+    with open(sorted(files)[-1]) as f:
+        rows = [(r["Kernel_Name"], int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in csv.DictReader(f)]
+    rows.sort(key=lambda r: r[1])
+    ends = [i for i, r in enumerate(rows) if "adam_kernel" in r[0]]
+    if len(ends) < 2:
+        return None
+    step = rows[ends[-2] + 1:ends[-1] + 1]
+    total = sum(e - s for _, s, e in step)
+    part = lambda names: sum(e - s for n, s, e in step if any(k in n for k in names))
+    lists, red = part(LIST_KERNELS), part(REDUCE_KERNELS)
+    return dict(step_kernel_ms=round(total / 1e6, 3), dispatches=len(step), list_build_ms=round(lists / 1e6, 3), reductions_ms=round(red / 1e6, 3),
+                list_build_share=round(lists / total, 4), reductions_share=round(red / total, 4))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rooms", type=int, default=8)
@@ -122,13 +163,14 @@ def main():
     ap.add_argument("--batch", type=int, default=6)
     ap.add_argument("--out", default=os.path.join(ROOT, "bench_out", "train_probe"))
     ap.add_argument("--limit", type=int, default=240, help="seconds each child may take")
+    ap.add_argument("--deterministic", action="store_true", help="time both modes; trace the deterministic one")
     ap.add_argument("--child", choices=["time", "trace"])
     a = ap.parse_args()
     if a.child:
         return child(a.child, a)
     os.makedirs(a.out, exist_ok=True)
     me = [sys.executable, os.path.abspath(__file__), "--rooms", str(a.rooms), "--steps", str(a.steps), "--warmup", str(a.warmup), "--points", str(a.points),
-          "--batch", str(a.batch)]
+          "--batch", str(a.batch)] + (["--deterministic"] if a.deterministic else [])
     result = {}
     for mode, prefix in (("time", []), ("trace", ["rocprofv3", "--kernel-trace", "--stats", "-d", a.out, "-o", "train", "--output-format", "csv", "--"])):
         cmd = ["timeout", "-k", "10", str(a.limit)] + prefix + me + ["--child", mode]
@@ -140,7 +182,8 @@ def main():
             return 1
         line = [l for l in p.stdout.splitlines() if l.startswith("TRAIN_PROBE ")]
         result[mode] = json.loads(line[-1][len("TRAIN_PROBE "):]) if line else None
-    print(json.dumps(dict(probe="train", timed=result["time"], traced_step_ms=(result["trace"] or {}).get("step_ms_events"), slowest_kernels=slowest_kernels(a.out))))
+    print(json.dumps(dict(probe="train", timed=result["time"], traced_step_ms=(result["trace"] or {}).get("step_ms_events"), slowest_kernels=slowest_kernels(a.out),
+                          deterministic_share=deterministic_share(a.out) if a.deterministic else None)))
     return 0
 
 
