@@ -751,6 +751,42 @@ int ssdr_scatter_add_rows_dev(const int32_t* d_idx, int B, int rows_per_b, int s
 int ssdr_pool_grad_rows_dev(const float* d_src, float* d_dsrc, int lds, int src_rows, const int32_t* d_idx, int B, int m_per_b, int C,
                             const float* d_out, const float* d_dout, int ldo, void* stream);
 
+/* ---- data-parallel training: one process per GPU, every rank a replica (csrc/train_exchange.hip, DESIGN section 21 "Data-parallel") ----
+ * The library links no collective library.  With an exchange set, _step_dev, _grads_dev and _forward_dev(is_training = 1) call `fn` where the ranks
+ * must meet; `fn` only ENQUEUES the collective on `stream` (the call's stream) and returns 0, the host reads no device value.  The step is then the
+ * step of ONE process over the union of all ranks' tiles: batch norm over all ranks' rows (forward and backward), the loss over the global number
+ * of valid rows, one gradient sum.  Ranks may hold different B; every rank must make the same calls in the same order.
+ *   SSDR_XCHG_GATHER: d_recv [world][count] <- every rank's d_send [count], in rank order.
+ *   SSDR_XCHG_SUM:    d_recv [count] (may equal d_send) <- the element-wise sum over the ranks, the same bits on every rank.
+ * Meeting points: per batch-normed unit one GATHER of [n_r | mean[C] | M2[C]] in the forward pass (merged by Chan's formula in rank order from
+ *   n = 0; the moving statistics take the global values, the unbiased factor n / (n - 1) the global count) and one GATHER of [dgamma[C] | dbeta[C]]
+ *   in the backward pass (summed in rank order; the norm's backward divides by the global count); one GATHER of the loss's three sums (d_loss,
+ *   d_accuracy are global and identical on every rank; status bit 0 only when NO rank has a valid row); ONE SUM over the whole gradient arena
+ *   before Adam (ranks other than 0 zero their gamma / beta gradients first: those are global already).  After it every rank holds the union's
+ *   gradient with the same bits, so replicas that start identical stay identical; weights are never broadcast.
+ *   _forward_dev(is_training = 0) and _apply_dev do not meet.
+ * ssdr_randla_train_set_exchange: fn NULL (with world <= 1): back to one process.  Refused (SSDR_ERR_INVALID) before anything changes: world < 1,
+ *   rank outside [0, world), fn NULL with world > 1.  ssdr_randla_train_exchange reads rank and world back (world 0: none set).
+ *   A callback that returns non-zero fails the call with SSDR_ERR_INVALID, "exchange failed".  The send [1 + 2 Cmax] and receive
+ *   [world][1 + 2 Cmax] buffers are part of ssdr_randla_train_workspace_bytes.  Without an exchange every call launches what it launched before.
+ * The merges as stand-alone pieces, enqueue only:
+ * ssdr_bn_stats_merge_dev: d_records f32 [world][1 + 2C] -> d_mean [C], d_invstd [C] = 1 / sqrt(M2 / n + 1e-6), d_count [1] = n; when
+ *   d_mov_mean / d_mov_var are not NULL (both or neither): moving -= (moving - x) * 0.01 with x the mean and the variance (times n / (n - 1) when
+ *   unbiased != 0 and n > 1).  A record with n_r = 0 is skipped.
+ * ssdr_rank_sums_merge_dev: d_records f32 [world][n] -> d_out[i] = ((0 + r0[i]) + r1[i]) + ...
+ * ssdr_randla_train_dropout_mask_range_dev: elements first .. first + n - 1 of the mask of (seed, step): a rank's mask is the slice of the union's.
+ *   first = 0 is ssdr_randla_train_dropout_mask_dev.
+ * Refused (SSDR_ERR_INVALID): NULL pointers, world < 1, C < 1, n < 1. */
+typedef int (*ssdr_exchange_fn)(void* user, int op, const float* d_send, float* d_recv, size_t count, void* stream);
+#define SSDR_XCHG_GATHER 0
+#define SSDR_XCHG_SUM    1
+int ssdr_randla_train_set_exchange(void* handle, ssdr_exchange_fn fn, void* user, int rank, int world);
+int ssdr_randla_train_exchange(void* handle, int* rank, int* world);
+int ssdr_bn_stats_merge_dev(const float* d_records, int world, int C, float* d_mean, float* d_invstd, float* d_count, float* d_mov_mean, float* d_mov_var,
+                            int unbiased, void* stream);
+int ssdr_rank_sums_merge_dev(const float* d_records, int world, int n, float* d_out, void* stream);
+int ssdr_randla_train_dropout_mask_range_dev(uint64_t seed, uint64_t step, uint64_t first, size_t n, uint8_t* d_mask, void* stream);
+
 /* ---- plain device memory for callers without their own allocator (tests, the ctypes mirror) ---------- */
 int ssdr_dev_alloc(size_t bytes, void** d_ptr);
 int ssdr_dev_free(void* d_ptr);

@@ -18,6 +18,7 @@
 // with reductions over inverse lists (scatter_det.hip) that add in a fixed order: then the gradients and the weights are the same bits every run.
 #include "ssdr_internal.hpp"
 #include "scatter_det.hpp"
+#include "train_exchange.hpp"
 #include <cmath>
 #include <cstring>
 #include <functional>
@@ -204,15 +205,17 @@ __global__ void bn_apply_kernel(BnArgs a) {
     a.out[r * a.ldo + c] = y;
 }
 
-// dz (in place of z) = gamma * invstd * (dY - dbeta / M - xhat * dgamma / M)
+// dz (in place of z) = gamma * invstd * (dY - dbeta / M - xhat * dgamma / M).  GLOBAL: dbeta and dgamma are sums over all ranks' rows and the row count
+// is the global one, read from the device (count[0], left by the forward pass's merge)
+template <bool GLOBAL>
 __global__ void bn_bwd_kernel(float* z, const float* da, const float* av, int lda, int act, const float* mean, const float* invstd, const float* gamma,
-                              const float* dbeta, const float* dgamma, int M, int C) {
+                              const float* dbeta, const float* dgamma, int M, int C, const float* count) {
     const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= (long)M * C) return;
     const int c = (int)(e % C); const long r = e / C;
     float dy = da[r * lda + c];
     if (act && !(av[r * lda + c] > 0.f)) dy *= LRELU;
-    const float xh = (z[e] - mean[c]) * invstd[c], inv_m = 1.f / (float)M;
+    const float xh = (z[e] - mean[c]) * invstd[c], inv_m = 1.f / (GLOBAL ? count[0] : (float)M);
     z[e] = gamma[c] * invstd[c] * (dy - dbeta[c] * inv_m - xh * dgamma[c] * inv_m);
 }
 
@@ -321,13 +324,15 @@ __global__ void pool_bwd_kernel(const float* src, float* dsrc, int lds, int src_
 
 // ---- dropout (keep_prob 0.5 after fc2, RandLANet.py:176-177) ----
 __device__ inline uint32_t mix32(uint32_t x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; }
-__global__ void dropout_mask_kernel(uint64_t seed, uint64_t step, long n, uint8_t* mask) {
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
+// mask[i] = the bit of element first + i
+__global__ void dropout_mask_kernel(uint64_t seed, uint64_t step, uint64_t first, long n, uint8_t* mask) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t e = first + (uint64_t)i;
     uint32_t h = mix32((uint32_t)seed ^ 0x9e3779b9u);
     h = mix32(h ^ (uint32_t)(seed >> 32)); h = mix32(h ^ (uint32_t)step); h = mix32(h ^ (uint32_t)(step >> 32));
     h = mix32(h ^ (uint32_t)e); h = mix32(h + (uint32_t)(e >> 32));
-    mask[e] = (uint8_t)(h >> 31);
+    mask[i] = (uint8_t)(h >> 31);
 }
 __global__ void dropout_fwd_kernel(const float* x, const uint8_t* mask, long n, float* y) {
     const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -377,7 +382,9 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(const float* logits, int
     }
     if (threadIdx.x == 0) for (int q = 0; q < 3; ++q) part[(long)blockIdx.x * 3 + q] = sh[q][0];
 }
-// out[0] = loss, out[1] = accuracy, out[2] = valid rows; no valid row: zeros and status bit 0
+// out[0] = loss, out[1] = accuracy, out[2] = valid rows; no valid row: zeros and status bit 0.  PACK: out[0 .. 2] = this rank's three sums (loss, valid,
+// correct) for the gather; loss_merge_kernel finishes
+template <bool PACK>
 __global__ __launch_bounds__(256) void loss_final_kernel(const float* part, int nblocks, float* out, float* d_loss, float* d_acc, int* status) {
     __shared__ float sh[3][256];
     float v[3] = {0.f, 0.f, 0.f};
@@ -389,6 +396,7 @@ __global__ __launch_bounds__(256) void loss_final_kernel(const float* part, int 
         __syncthreads();
     }
     if (threadIdx.x == 0) {
+        if (PACK) { for (int q = 0; q < 3; ++q) out[q] = sh[q][0]; return; }
         const float n = sh[1][0];
         const float loss = n > 0.f ? sh[0][0] / n : 0.f, acc = n > 0.f ? sh[2][0] / n : 0.f;
         out[0] = loss; out[1] = acc; out[2] = n;
@@ -397,7 +405,20 @@ __global__ __launch_bounds__(256) void loss_final_kernel(const float* part, int 
         if (!(n > 0.f)) atomicOr(status, 1);
     }
 }
-// dlogits = (softmax - onehot(pseudo)) * weight * activation / valid rows
+// records [world][3] = every rank's (loss, valid, correct) sums, added in rank order from 0: the same out / d_loss / d_acc on every rank, status bit 0
+// only when no rank has a valid row
+__global__ void loss_merge_kernel(const float* records, int world, float* out, float* d_loss, float* d_acc, int* status) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    float v[3] = {0.f, 0.f, 0.f};
+    for (int r = 0; r < world; ++r) for (int q = 0; q < 3; ++q) v[q] += records[r * 3 + q];
+    const float n = v[1];
+    const float loss = n > 0.f ? v[0] / n : 0.f, acc = n > 0.f ? v[2] / n : 0.f;
+    out[0] = loss; out[1] = acc; out[2] = n;
+    if (d_loss) *d_loss = loss;
+    if (d_acc) *d_acc = acc;
+    if (!(n > 0.f)) atomicOr(status, 1);
+}
+// dlogits = (softmax - onehot(pseudo)) * weight * activation / valid rows (of all ranks, when an exchange is set: fin[2] is global then)
 __global__ void loss_grad_kernel(const float* logits, int C, long M, const float* row_w, const int32_t* row_cls, const float* fin, float* dlogits) {
     const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= M) return;
@@ -443,6 +464,10 @@ struct Train {
     LossTables tb{};
     float lr = 0.01f; long step = 0;
     bool params_set = false;
+    // data-parallel mode (train_exchange.hpp): the callback, the collectives' send [1 + 2 cmax] and receive [world][1 + 2 cmax] buffers, and the table
+    // of the (offset, length) ranges of G that hold gamma / beta gradients (global before the gradient sum: ranks other than 0 zero them)
+    Exchange xg; DevBuf xsend, xrecv, gb_table; std::vector<long> gb_ranges; int cmax = 1;
+    long xchg_floats() const { return xg.world > 0 ? (1L + xg.world) * xchg_record_floats(cmax) : 0; }
     // deterministic mode: the inverse lists of neigh / pool / interp of every level (list 3 i + 0 / 1 / 2), laid out by det_layout
     struct DetList { long off_at, pos_at; int src_rows, rows_per_b; };
     bool det = false, planned_det = false;
@@ -488,7 +513,9 @@ void build_units(Train& m) {
             u.obeta = m.n_par; m.tensors.push_back({(int)i, 3, 1, u.out, u.obeta}); m.n_par += u.out;
             u.omean = m.n_stat; m.tensors.push_back({(int)i, 4, 1, u.out, u.omean}); m.n_stat += u.out;
             u.ovar = m.n_stat; m.tensors.push_back({(int)i, 5, 1, u.out, u.ovar}); m.n_stat += u.out;
-            u.obs = m.n_bs; m.n_bs += 2 * u.out;
+            u.obs = m.n_bs; m.n_bs += 2 * u.out + 1;            // mean, 1 / std, and the global row count (one float; data-parallel mode)
+            m.gb_ranges.push_back(u.og); m.gb_ranges.push_back(2L * u.out);      // gamma and beta lie side by side
+            m.cmax = std::max(m.cmax, u.out);
         }
     }
 }
@@ -529,6 +556,13 @@ struct Runner {
     static long w_rs(const Unit& u) { return u.transposed ? 1 : u.out; }
     static long w_cs(const Unit& u) { return u.transposed ? u.in : 1; }
 
+    // data-parallel mode: this pass meets the other ranks
+    bool meets() const { return m.xg.world > 0 && training; }
+    int exchange(int op, const float* send, float* recv, size_t count) {
+        if (m.xg.fn(m.xg.user, op, send, recv, count, (void*)s) != 0) { set_error("randla_train: exchange failed"); return SSDR_ERR_INVALID; }
+        return SSDR_OK;
+    }
+    // RED_STATS: out0 = mean, out1 = 1 / std, and the row count behind them.  RED_BNBWD: out0 = dbeta, out1 = dgamma with out1 + C == out0.
     template <int MODE> int reduce(RedArgs a, float* out0, float* out1, float* mm, float* mv, int unbiased) {
         if (dry) return SSDR_OK;
         int ct = 8; while (ct < 64 && ct < a.C) ct *= 2;
@@ -538,6 +572,19 @@ struct Runner {
         const int nchunks = (a.M + a.chunk - 1) / a.chunk;
         a.part = m.part.as<float>();
         hipLaunchKernelGGL((reduce_kernel<MODE>), dim3(nchunks, blocks_for(a.C, ct)), dim3(256), 0, s, a);
+        if (MODE != RED_SUM && meets()) {
+            // one launch in front of the collective (the chunks' combine, into the send buffer), one behind it (the ranks' merge)
+            float* send = m.xsend.as<float>(); float* recv = m.xrecv.as<float>();
+            SSDR_HIP(hipGetLastError());
+            if (MODE == RED_STATS) {
+                SSDR_TRY(xchg_pack_stats(a.part, nchunks, a.chunk, a.M, a.C, send, s));
+                SSDR_TRY(exchange(SSDR_XCHG_GATHER, send, recv, (size_t)xchg_record_floats(a.C)));
+                return xchg_merge_stats(recv, m.xg.world, a.C, out0, out1, out1 + a.C, mm, mv, unbiased, s);
+            }
+            SSDR_TRY(xchg_pack_sums(a.part, nchunks, a.C, send, 1, s));
+            SSDR_TRY(exchange(SSDR_XCHG_GATHER, send, recv, (size_t)2 * a.C));
+            return xchg_merge_sums(recv, m.xg.world, 2 * a.C, out1, s);
+        }
         hipLaunchKernelGGL((combine_kernel<MODE>), dim3(blocks_for(a.C, 64)), dim3(64), 0, s, a.part, nchunks, a.chunk, a.M, a.C, out0, out1, mm, mv, unbiased);
         SSDR_HIP(hipGetLastError());
         return SSDR_OK;
@@ -586,7 +633,8 @@ struct Runner {
         const float* mean = m.BS.as<float>() + u.obs; const float* invstd = mean + u.out;
         RedArgs r{}; r.z = z; r.ldz = u.out; r.da = y.g; r.av = y.v; r.lda = y.ld; r.act = act; r.mean = mean; r.invstd = invstd; r.M = M; r.C = u.out;
         SSDR_TRY(reduce<RED_BNBWD>(r, m.grd(u.obeta), m.grd(u.og), nullptr, nullptr, 0));
-        hipLaunchKernelGGL(bn_bwd_kernel, dim3(blocks_for((long)M * u.out)), dim3(256), 0, s, z, y.g, y.v, y.ld, act, mean, invstd, m.par(u.og), m.grd(u.obeta), m.grd(u.og), M, u.out);
+        if (meets()) hipLaunchKernelGGL(bn_bwd_kernel<true>, dim3(blocks_for((long)M * u.out)), dim3(256), 0, s, z, y.g, y.v, y.ld, act, mean, invstd, m.par(u.og), m.grd(u.obeta), m.grd(u.og), M, u.out, invstd + u.out);
+        else hipLaunchKernelGGL(bn_bwd_kernel<false>, dim3(blocks_for((long)M * u.out)), dim3(256), 0, s, z, y.g, y.v, y.ld, act, mean, invstd, m.par(u.og), m.grd(u.obeta), m.grd(u.og), M, u.out, (const float*)nullptr);
         return SSDR_OK;
     }
 
@@ -811,7 +859,14 @@ int run(Train* m, const StepIn& in, int is_training, int mode, float* d_logits, 
     float* row_w = m->lpart.as<float>(); int32_t* row_cls = reinterpret_cast<int32_t*>(row_w + rows0); float* lp = row_w + 2 * rows0;
     const int nb = (int)blocks_for(rows0);
     hipLaunchKernelGGL(loss_rows_kernel, dim3(nb), dim3(256), 0, s, logits.v, m->C, in.d_labels, in.d_activation, in.d_pseudo, rows0, m->tb, row_w, row_cls, lp, status);
-    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, s, lp, nb, m->fin.as<float>(), d_loss, d_acc, status);
+    if (r.meets()) {
+        hipLaunchKernelGGL(loss_final_kernel<true>, dim3(1), dim3(256), 0, s, lp, nb, m->xsend.as<float>(), (float*)nullptr, (float*)nullptr, status);
+        SSDR_HIP(hipGetLastError());
+        SSDR_TRY(r.exchange(SSDR_XCHG_GATHER, m->xsend.as<float>(), m->xrecv.as<float>(), 3));
+        hipLaunchKernelGGL(loss_merge_kernel, dim3(1), dim3(64), 0, s, m->xrecv.as<float>(), m->xg.world, m->fin.as<float>(), d_loss, d_acc, status);
+    } else {
+        hipLaunchKernelGGL(loss_final_kernel<false>, dim3(1), dim3(256), 0, s, lp, nb, m->fin.as<float>(), d_loss, d_acc, status);
+    }
     hipLaunchKernelGGL(loss_grad_kernel, dim3(blocks_for(rows0)), dim3(256), 0, s, logits.v, m->C, rows0, row_w, row_cls, m->fin.as<float>(), logits.g);
     SSDR_HIP(hipGetLastError());
     // the lists are built from the index arrays of THIS call, every call: a feeder hands out the same buffers with new contents
@@ -825,6 +880,11 @@ int run(Train* m, const StepIn& in, int is_training, int mode, float* d_logits, 
         }
     }
     for (size_t i = r.tape.size(); i-- > 0;) SSDR_TRY(r.tape[i]());
+    if (r.meets()) {
+        // ONE sum over the whole arena.  gamma / beta gradients are global already: every rank but 0 zeroes them (adding 0 is exact)
+        if (m->xg.rank != 0) SSDR_TRY(xchg_zero_ranges(m->G.as<float>(), m->gb_table.as<long>(), (int)(m->gb_ranges.size() / 2), s));
+        SSDR_TRY(r.exchange(SSDR_XCHG_SUM, m->G.as<float>(), m->G.as<float>(), (size_t)m->n_par));
+    }
     SSDR_HIP(hipEventRecord(m->ev[2], s));
     if (mode & 2) {
         m->step += 1;
@@ -868,6 +928,10 @@ int ssdr_randla_train_create(int num_layers, const int32_t* d_out, int k_n, int 
     for (int c = 0; c < 64; ++c) { m->tb.remap[c] = c < num_classes ? c : 0; m->tb.ignored[c] = 0; }
     for (int c = 0; c < 32; ++c) m->tb.cw[c] = 1.f;
     for (hipEvent_t& e : m->ev) if (hipEventCreate(&e) != hipSuccess) return fail(SSDR_ERR_HIP);
+    if (!m->gb_ranges.empty()) {
+        const size_t tb = sizeof(long) * m->gb_ranges.size();
+        if (m->gb_table.reserve(tb) != SSDR_OK || hipMemcpy(m->gb_table.p, m->gb_ranges.data(), tb, hipMemcpyHostToDevice) != hipSuccess) return fail(SSDR_ERR_HIP);
+    }
     *handle = m;
     return SSDR_OK;
 }
@@ -978,7 +1042,7 @@ int64_t ssdr_randla_train_step_count(void* handle) { return handle ? (int64_t)st
 /* bytes of the activation + gradient workspaces laid out by the last call */
 size_t ssdr_randla_train_workspace_bytes(void* handle) {
     Train* m = static_cast<Train*>(handle);
-    return m ? (size_t)(m->act_floats + m->grad_floats) * 4 + (m->det && !m->dl.empty() ? m->det_bytes() : 0) : 0;
+    return m ? (size_t)(m->act_floats + m->grad_floats) * 4 + (m->det && !m->dl.empty() ? m->det_bytes() : 0) + (m->act_floats ? (size_t)m->xchg_floats() * 4 : 0) : 0;
 }
 
 /* on != 0: the three backward scatters become reductions over inverse lists (scatter_det.hip), the same bits every run.  Off (the default) launches
@@ -1001,11 +1065,38 @@ int ssdr_randla_train_last_ms(void* handle, float* out3) {
     return SSDR_OK;
 }
 
-int ssdr_randla_train_dropout_mask_dev(uint64_t seed, uint64_t step, size_t n, uint8_t* d_mask, void* stream) {
+/* elements first .. first + n - 1 of the mask of (seed, step): a rank's slice of the union's mask */
+int ssdr_randla_train_dropout_mask_range_dev(uint64_t seed, uint64_t step, uint64_t first, size_t n, uint8_t* d_mask, void* stream) {
     if (!d_mask || n == 0) { set_error("randla_train_dropout_mask: bad arguments"); return SSDR_ERR_INVALID; }
     SSDR_TRY(ensure_init());
-    hipLaunchKernelGGL(dropout_mask_kernel, dim3(blocks_for((long)n)), dim3(256), 0, pick_stream(stream), seed, step, (long)n, d_mask);
+    hipLaunchKernelGGL(dropout_mask_kernel, dim3(blocks_for((long)n)), dim3(256), 0, pick_stream(stream), seed, step, first, (long)n, d_mask);
     SSDR_HIP(hipGetLastError());
+    return SSDR_OK;
+}
+int ssdr_randla_train_dropout_mask_dev(uint64_t seed, uint64_t step, size_t n, uint8_t* d_mask, void* stream) {
+    return ssdr_randla_train_dropout_mask_range_dev(seed, step, 0, n, d_mask, stream);
+}
+
+/* Data-parallel mode (include/ssdr_al.h): fn is called, on the calling thread, wherever the ranks must meet, and only enqueues on the call's stream.
+ * fn NULL with world 1: back to one process. */
+int ssdr_randla_train_set_exchange(void* handle, ssdr_exchange_fn fn, void* user, int rank, int world) {
+    Train* m = static_cast<Train*>(handle);
+    if (!m) { set_error("randla_train_set_exchange: bad handle"); return SSDR_ERR_INVALID; }
+    if (world < 1 || rank < 0 || rank >= world) { set_error("randla_train_set_exchange: rank %d of world %d", rank, world); return SSDR_ERR_INVALID; }
+    if (!fn && world > 1) { set_error("randla_train_set_exchange: world %d needs a callback", world); return SSDR_ERR_INVALID; }
+    if (!fn) { m->xg = Exchange{}; return SSDR_OK; }
+    // nothing that was enqueued may still use the buffers when they move
+    SSDR_HIP(hipDeviceSynchronize());
+    SSDR_TRY(m->xsend.reserve(sizeof(float) * (size_t)xchg_record_floats(m->cmax)));
+    SSDR_TRY(m->xrecv.reserve(sizeof(float) * (size_t)world * (size_t)xchg_record_floats(m->cmax)));
+    m->xg = Exchange{fn, user, rank, world};
+    return SSDR_OK;
+}
+int ssdr_randla_train_exchange(void* handle, int* rank, int* world) {
+    Train* m = static_cast<Train*>(handle);
+    if (!m) { set_error("randla_train_exchange: bad handle"); return SSDR_ERR_INVALID; }
+    if (rank) *rank = m->xg.rank;
+    if (world) *world = m->xg.world;
     return SSDR_OK;
 }
 

@@ -16,6 +16,24 @@ import numpy as np
 from . import _lib
 
 
+class RawView:
+    """``count`` elements at a raw device pointer, not owned: what a callback of the library is handed (``Trainer``'s exchange callback gets
+    ``const float* d_send, float* d_recv, size_t count``).  Everything ``Comm.view`` needs of a DevArray, so the collectives take either."""
+
+    def __init__(self, ptr, count, dtype=np.float32):
+        self.ptr, self.shape, self.dtype = int(ptr), (int(count),), np.dtype(dtype)
+        self.nbytes = int(count) * self.dtype.itemsize
+
+    @property
+    def __cuda_array_interface__(self):
+        return {"shape": self.shape, "typestr": self.dtype.str, "data": (self.ptr, False), "version": 2, "strides": None}
+
+    def host_view(self):
+        """CPU logic build only (device memory == host memory there)"""
+        import ctypes as C
+        return np.frombuffer((C.c_char * self.nbytes).from_address(self.ptr), self.dtype)
+
+
 class Comm:
     def __init__(self, dist, device):
         import torch
@@ -23,12 +41,27 @@ class Comm:
         self.rank, self.world = dist.get_rank(), dist.get_world_size()
         self.cuda = str(device).startswith("cuda")
         self._ext = {}
+        self._raw = {}
 
     def view(self, arr):
-        """torch tensor sharing the memory of a DevArray (no copy)."""
+        """torch tensor sharing the memory of a DevArray or a RawView (no copy); a tensor (``raw_view``'s) is returned as it is."""
+        if isinstance(arr, self.torch.Tensor):
+            return arr
         if self.cuda:
             return self.torch.as_tensor(arr, device=self.device)
         return self.torch.from_numpy(arr.host_view())              # CPU logic build: device memory is host memory
+
+    def raw_view(self, ptr, count, dtype=np.float32):
+        """Zero-copy torch tensor over ``count`` elements at the raw device pointer ``ptr`` (``__cuda_array_interface__`` on the GPU, host memory on
+        the CPU logic build); ``allreduce_sum_`` and ``allgather_`` take it wherever they take a DevArray.  The same (ptr, count) gives the same
+        tensor again: a training step asks for the same few buffers ninety times."""
+        key = (int(ptr), int(count), np.dtype(dtype).str)
+        t = self._raw.get(key)
+        if t is None:
+            if len(self._raw) > 4096:
+                self._raw.clear()
+            t = self._raw[key] = self.view(RawView(ptr, count, dtype))
+        return t
 
     def on_stream(self, stream):
         """Context in which collectives are ordered on the library stream `stream` (None = the library's main stream)."""
@@ -45,12 +78,12 @@ class Comm:
         return self.torch.cuda.stream(self._ext[key])
 
     def allreduce_sum_(self, arr, stream=None):
-        """In-place sum over ranks of a DevArray."""
+        """In-place sum over ranks of a DevArray (or a ``raw_view``)."""
         with self.on_stream(stream):
             self.dist.all_reduce(self.view(arr))
 
     def allgather_(self, arr_in, arr_out, stream=None):
-        """arr_out [world, *arr_in.shape] <- arr_in of every rank, in rank order (equal sizes: callers pad)."""
+        """arr_out [world, *arr_in.shape] <- arr_in of every rank, in rank order (equal sizes: callers pad).  DevArrays or ``raw_view``s."""
         with self.on_stream(stream):
             self.dist.all_gather_into_tensor(self.view(arr_out).reshape(-1), self.view(arr_in).reshape(-1)) if self.cuda else \
                 self.dist.all_gather(list(self.view(arr_out).reshape(self.world, -1).unbind(0)), self.view(arr_in).reshape(-1))

@@ -5,7 +5,12 @@ weighted cross entropy on the pseudo labels, the backward pass and tf.train.Adam
 Weights travel as the reference-named dict that ``randlanet.Network.load`` takes (entries ``W``, ``b``, ``bn = (gamma, beta, mean, var)``,
 ``transposed``), raw and unfolded.  By default the scatter-adds of the backward pass are float atomics: gradients and updated weights differ in
 their low bits from run to run, forward values (logits, loss, accuracy of given weights) do not.  ``Trainer(..., deterministic=True)`` (or
-``set_deterministic``) replaces them with reductions in a fixed order: the same inputs then give the same bits every run."""
+``set_deterministic``) replaces them with reductions in a fixed order: the same inputs then give the same bits every run.
+
+Data-parallel: ``Trainer(..., comm=distributed.Comm)`` (or ``set_comm``) trains one replica per process on that process's share of the batch, and the
+step equals the step of ONE process over the union of all ranks' tiles: batch norm over all ranks' rows (forward and backward), the loss over the
+global number of valid rows, one gradient sum over ``comm`` ("Data-parallel").  Weights are never broadcast: the replicas stay
+identical only if they start identical, so every rank must ``load`` the same weights (and the same ``load_state``)."""
 import ctypes as C
 
 import numpy as np
@@ -16,6 +21,8 @@ from .helper_tool import ConfigS3DIS
 from .synthetic import layer_specs
 
 KINDS = ("W", "b", "gamma", "beta", "mean", "var")
+XCHG_GATHER, XCHG_SUM = 0, 1                                  # SSDR_XCHG_* (include/ssdr_al.h)
+EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)      # ssdr_exchange_fn
 
 
 def _bind(L):
@@ -49,15 +56,24 @@ def _bind(L):
     L.ssdr_randla_train_status.argtypes = [vp, C.POINTER(i32)]
     L.ssdr_randla_train_set_deterministic.argtypes = [vp, i32]
     L.ssdr_randla_train_deterministic.argtypes = [vp]
+    L.ssdr_randla_train_set_exchange.argtypes = [vp, EXCHANGE_FN, vp, i32, i32]
+    L.ssdr_randla_train_exchange.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.ssdr_randla_train_dropout_mask_range_dev.argtypes = [u64, u64, u64, sz, vp, vp]
+    L.ssdr_bn_stats_merge_dev.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    L.ssdr_rank_sums_merge_dev.argtypes = [vp, i32, i32, vp, vp]
     L._train_bound = True
     return L
 
 
 class Trainer:
     """``Trainer(config).load(weights)``, then ``step(batch)`` per ``TrainFeeder`` batch, ``loss()`` / ``accuracy()`` when a number is wanted and
-    ``export_to(network)`` for ``infer``, ``VoteTester`` or ``WholeCloudPredictor``.  ``train_round(feeder, epochs, tester)`` is ``Network.train``."""
+    ``export_to(network)`` for ``infer``, ``VoteTester`` or ``WholeCloudPredictor``.  ``train_round(feeder, epochs, tester)`` is ``Network.train``.
 
-    def __init__(self, config=ConfigS3DIS, in_dim=6, class_weights=None, ignored_labels=(), lr=None, seed=0, deterministic=False):
+    comm: a ``distributed.Comm`` (one process per GPU).  Every rank steps on its own tiles and ends each step with the weights of one process
+    stepping on all ranks' tiles, the same bits on every rank.  The replicas stay identical only if they start identical: every rank must ``load``
+    the same weights.  Every rank must make the same calls in the same order (a rank that skips a step leaves the others waiting in a collective)."""
+
+    def __init__(self, config=ConfigS3DIS, in_dim=6, class_weights=None, ignored_labels=(), lr=None, seed=0, deterministic=False, comm=None):
         self.config, self.in_dim, self.seed = config, int(in_dim), int(seed)
         self.L, self.Cn = int(config.num_layers), int(config.num_classes)
         self._h = C.c_void_p()
@@ -85,8 +101,11 @@ class Trainer:
         self._loss, self._acc = DevArray((1,), np.float32), DevArray((1,), np.float32)
         self._mask = None
         self._last_stream = None
+        self._comm, self._hook, self._hook_error, self.exchanges = None, None, None, 0
         if deterministic:
             self.set_deterministic(True)
+        if comm is not None:
+            self.set_comm(comm)
 
     def __del__(self):
         try:
@@ -192,6 +211,48 @@ class Trainer:
     def deterministic(self):
         return bool(self._lib.ssdr_randla_train_deterministic(self._h))
 
+    def set_comm(self, comm):
+        """comm: a ``distributed.Comm``: from the next call on, ``step`` / ``grads_arrays`` / ``forward_arrays(is_training=True)`` meet the other ranks
+        (class docstring); None: back to one process.  The collectives are enqueued on the call's stream by a callback of the library; an exception
+        raised in it fails the call and is raised again by the call.  Every rank must hold the same weights when this is set."""
+        if comm is None:
+            _lib.check(self._lib.ssdr_randla_train_set_exchange(self._h, EXCHANGE_FN(), None, 0, 1))
+            self._comm = self._hook = None
+            return self
+
+        def hook(user, op, send, recv, count, stream):
+            try:
+                if op == XCHG_GATHER:
+                    comm.allgather_(comm.raw_view(send, count), comm.raw_view(recv, count * comm.world), stream)
+                elif op == XCHG_SUM:
+                    out = comm.raw_view(recv, count)
+                    if send != recv:
+                        with comm.on_stream(stream):
+                            out.copy_(comm.raw_view(send, count))
+                    comm.allreduce_sum_(out, stream)
+                else:
+                    raise ValueError("Trainer: unknown exchange op %d" % op)
+                self.exchanges += 1
+                return 0
+            except BaseException as e:                      # nothing may unwind through the library's frames
+                self._hook_error = e
+                return 1
+        cb = EXCHANGE_FN(hook)
+        _lib.check(self._lib.ssdr_randla_train_set_exchange(self._h, cb, None, int(comm.rank), int(comm.world)))
+        self._comm, self._hook = comm, cb                   # the library keeps the pointer: the trampoline lives as long as it is set
+        return self
+
+    @property
+    def comm(self):
+        return self._comm
+
+    def _check(self, status):
+        """_lib.check, after the exception the exchange callback stored during the call (if any)"""
+        err, self._hook_error = self._hook_error, None
+        if err is not None:
+            raise err
+        _lib.check(status)
+
     def workspace_bytes(self):
         return int(self._lib.ssdr_randla_train_workspace_bytes(self._h))
 
@@ -214,13 +275,17 @@ class Trainer:
         ptrs = [arr(*[a.ptr for a in lst]) for lst in (xyz, neigh, pool, up)]
         return B, N, r, ptrs, feat, labels, act, pse
 
-    def make_mask(self, B, N, stream=None, step=None):
-        """the dropout mask of (seed, step) for a [B, N] batch, on the device (u8 [B N, 32])"""
+    def make_mask(self, B, N, stream=None, step=None, first_row=None):
+        """the dropout mask of (seed, step) for a [B, N] batch, on the device (u8 [B N, 32]).  first_row: the batch's first ELEMENT in the mask of
+        the union of all ranks' batches; with a communicator it defaults to ``comm.rank * B * N * 32`` (every rank holds B tiles: a rank's mask is
+        then its slice of the union's), without one to 0.  Ranks with uneven shares pass it, or their own ``mask=`` to the step."""
         n = B * N * 32
         if self._mask is None or self._mask.shape != (n,):
             self._mask = DevArray((n,), np.uint8)
         t = self.step_count() if step is None else int(step)
-        _lib.check(self._lib.ssdr_randla_train_dropout_mask_dev(self.seed, t, n, self._mask.ptr, stream))
+        if first_row is None:
+            first_row = self._comm.rank * n if self._comm is not None else 0
+        _lib.check(self._lib.ssdr_randla_train_dropout_mask_range_dev(self.seed, t, int(first_row), n, self._mask.ptr, stream))
         return self._mask
 
     def _call(self, fn, arrays, stream, mask):
@@ -231,8 +296,8 @@ class Trainer:
             mask = self.make_mask(B, N, stream)
         self._keep = (arrays, mask, ptrs)            # the launches read them after this call returns
         self._last_stream = stream
-        _lib.check(fn(self._h, B, N, feat.ptr, ptrs[0], _lib.ptr(r), ptrs[1], ptrs[2], ptrs[3], labels.ptr, act.ptr, pse.ptr, mask.ptr,
-                      self._loss.ptr, self._acc.ptr, stream))
+        self._check(fn(self._h, B, N, feat.ptr, ptrs[0], _lib.ptr(r), ptrs[1], ptrs[2], ptrs[3], labels.ptr, act.ptr, pse.ptr, mask.ptr,
+                       self._loss.ptr, self._acc.ptr, stream))
 
     def step_arrays(self, arrays, stream=None, mask=None):
         """One training step on device arrays in the reference's input_list order: [xyz_0.., neigh_0.., pool_0.., up_0.., features, labels,
@@ -261,8 +326,8 @@ class Trainer:
         logits, f32 = DevArray((B * N, self.Cn), np.float32), DevArray((B * N, 32), np.float32)
         self._keep = (arrays, mask, ptrs)
         self._last_stream = stream
-        _lib.check(self._lib.ssdr_randla_train_forward_dev(self._h, B, N, feat.ptr, ptrs[0], _lib.ptr(r), ptrs[1], ptrs[2], ptrs[3],
-                                                           mask.ptr if mask is not None else None, 1 if is_training else 0, logits.ptr, f32.ptr, stream))
+        self._check(self._lib.ssdr_randla_train_forward_dev(self._h, B, N, feat.ptr, ptrs[0], _lib.ptr(r), ptrs[1], ptrs[2], ptrs[3],
+                                                            mask.ptr if mask is not None else None, 1 if is_training else 0, logits.ptr, f32.ptr, stream))
         return logits, f32
 
     def loss(self):
@@ -292,10 +357,19 @@ class Trainer:
     def train_round(self, feeder, epochs, tester=None):
         """``Network.train`` (RandLANet.py:217-282): per epoch the feeder's batches, then the decay; from int(0.4 epochs) on the voting evaluation
         through ``tester`` (an ``evaluate.VoteTester``, whose network is reloaded from this trainer).  Keeps the best state in ``best_state`` and
-        returns (best_mIoU, best_OA).  Starts from config.learning_rate (reset_lr, :213-215)."""
+        returns (best_mIoU, best_OA).  Starts from config.learning_rate (reset_lr, :213-215).
+
+        With a communicator every rank's feeder holds that rank's clouds and every rank steps once per batch, so all feeders must give the same number
+        of batches per epoch: the ranks compare their counts before each epoch and EVERY rank raises when they differ (unequal counts would leave
+        the longer ranks waiting in a collective for ever).  The evaluation stays replicated: each rank evaluates its own tester."""
         self.set_lr(float(getattr(self.config, "learning_rate", self.lr)))
         best_miou, best_oa, self.best_state = 0, 0, None
         for epoch in range(1, epochs + 1):
+            if self._comm is not None:
+                counts = self._comm.allgather_host(np.asarray([int(feeder.steps_per_epoch)], np.int64)).reshape(-1)
+                if len(set(counts.tolist())) != 1:
+                    raise ValueError("Trainer.train_round: the ranks' feeders give %s batches per epoch; every rank must step the same number of times"
+                                     % counts.tolist())
             for batch in feeder.epoch_batches(None):
                 self.step(batch)
             self.decay(epoch)

@@ -12,7 +12,11 @@ child runs in deterministic mode: from the per-dispatch kernel trace of its last
 builds (key generation, the radix sort, the offsets) and the two reductions take.  The FLOP count is computed from the shapes (every dense layer: 2 M in out forward, the same again for dW and for dX
 where the input has a gradient; the attention softmax and the other element-wise work are not counted) and set against the float32 vector and
 matrix peaks of the MI355X, which are the same 157.3 TFLOP/s.
-Usage: python tools/train_probe.py [--deterministic] [--rooms 8] [--steps 5] [--warmup 2] [--points 40960] [--batch 6] [--out bench_out/train_probe]"""
+With --comm only the timed child runs: it measures the hook-less step, then joins an RCCL process group of world 1 in the same process, sets it on
+the SAME trainer (Trainer.set_comm) and measures the data-parallel step: forward / backward / update, the collectives per step, and the host's
+enqueue time per step (until step_arrays returns) beside the step's time on the GPU: while the first is the smaller one the callbacks run ahead of
+the GPU's queue and their cost on the host is hidden.
+Usage: python tools/train_probe.py [--deterministic | --comm] [--rooms 8] [--steps 5] [--warmup 2] [--points 40960] [--batch 6] [--out bench_out/train_probe]"""
 import argparse
 import csv
 import glob
@@ -63,6 +67,11 @@ def child(mode, a):
     class cfg(ConfigS3DIS):
         num_points = a.points
         batch_size = a.batch
+    if a.comm and mode == "time":                    # the framework takes the device first, as in the sharded round's workers: one HIP runtime per process
+        import torch
+        import torch.distributed as dist
+        torch.cuda.set_device(0)
+        dist.init_process_group("nccl", device_id=torch.device("cuda", 0))
     _lib.check(_lib.lib().ssdr_init(0))
     rooms = []
     for i in range(a.rooms):
@@ -84,13 +93,16 @@ def child(mode, a):
             tr.step_arrays(arrays)
         _lib.sync()
         split, wall = [], []
+        del enqueue[:]
         for _ in range(steps):
             t0 = time.perf_counter()
             tr.step_arrays(arrays)
+            enqueue.append(1e3 * (time.perf_counter() - t0))
             _lib.sync()
             wall.append(1e3 * (time.perf_counter() - t0))
             split.append(tr.last_ms())
         return split, wall
+    enqueue = []
     if a.deterministic and mode == "trace":
         tr.set_deterministic(True)
     split, wall = timed()
@@ -102,12 +114,26 @@ def child(mode, a):
         det = dict(step_ms_events=round(med([sum(s) for s in dsplit]), 3), step_ms_host=round(med(dwall), 3),
                    forward_ms=round(med([s[0] for s in dsplit]), 3), backward_ms=round(med([s[1] for s in dsplit]), 3), update_ms=round(med([s[2] for s in dsplit]), 3),
                    workspace_gib=round(tr.workspace_bytes() / 2.0 ** 30, 3), workspace_growth_mib=round((tr.workspace_bytes() - ws_default) / 2.0 ** 20, 1))
+    plain_enqueue = med(enqueue)
+    dp = None
+    if a.comm and mode == "time":                    # the same trainer, the same batch, through RCCL at world 1
+        from ssdr_al.distributed import Comm
+        tr.set_comm(Comm(dist, "cuda"))
+        before = tr.exchanges
+        csplit, cwall = timed()
+        per_step = (tr.exchanges - before) // (a.warmup + steps)
+        dp = dict(world=1, step_ms_events=round(med([sum(s) for s in csplit]), 3), step_ms_host=round(med(cwall), 3), host_enqueue_ms=round(med(enqueue), 3),
+                  forward_ms=round(med([s[0] for s in csplit]), 3), backward_ms=round(med([s[1] for s in csplit]), 3), update_ms=round(med([s[2] for s in csplit]), 3),
+                  collectives_per_step=int(per_step), workspace_gib=round(tr.workspace_bytes() / 2.0 ** 30, 3))
+        tr.set_comm(None)
+        _lib.sync()
+        dist.destroy_process_group()
     loss = tr.loss()
     assert np.isfinite(loss) and tr.status() == 0
     fwd, bwd = dense_flops(cfg, cfg.batch_size, tr.specs)
     step_ms = med([sum(s) for s in split])
     out = dict(mode=mode, deterministic=bool(tr.deterministic) if det is None else None, deterministic_mode=det, B=cfg.batch_size, N=cfg.num_points, steps=steps, warmup=a.warmup, loss=loss,
-               step_ms_events=round(step_ms, 3), step_ms_host=round(med(wall), 3),
+               step_ms_events=round(step_ms, 3), step_ms_host=round(med(wall), 3), host_enqueue_ms=round(plain_enqueue, 3), data_parallel=dp,
                forward_ms=round(med([s[0] for s in split]), 3), backward_ms=round(med([s[1] for s in split]), 3), update_ms=round(med([s[2] for s in split]), 3),
                dense_gflop=dict(forward=round(fwd / 1e9, 2), backward=round(bwd / 1e9, 2)),
                tflops=round((fwd + bwd) / (step_ms * 1e-3) / 1e12, 3), share_of_f32_peak=round((fwd + bwd) / (step_ms * 1e-3) / PEAK_F32, 4),
@@ -164,17 +190,21 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "bench_out", "train_probe"))
     ap.add_argument("--limit", type=int, default=240, help="seconds each child may take")
     ap.add_argument("--deterministic", action="store_true", help="time both modes; trace the deterministic one")
+    ap.add_argument("--comm", action="store_true", help="time the step through RCCL at world 1 against the hook-less step, in the same process")
+    ap.add_argument("--port", type=int, default=29631)
     ap.add_argument("--child", choices=["time", "trace"])
     a = ap.parse_args()
     if a.child:
         return child(a.child, a)
     os.makedirs(a.out, exist_ok=True)
     me = [sys.executable, os.path.abspath(__file__), "--rooms", str(a.rooms), "--steps", str(a.steps), "--warmup", str(a.warmup), "--points", str(a.points),
-          "--batch", str(a.batch)] + (["--deterministic"] if a.deterministic else [])
+          "--batch", str(a.batch)] + (["--deterministic"] if a.deterministic else []) + (["--comm"] if a.comm else [])
     result = {}
-    for mode, prefix in (("time", []), ("trace", ["rocprofv3", "--kernel-trace", "--stats", "-d", a.out, "-o", "train", "--output-format", "csv", "--"])):
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(a.port), RANK="0", LOCAL_RANK="0", WORLD_SIZE="1") if a.comm else None
+    runs = (("time", []), ("trace", ["rocprofv3", "--kernel-trace", "--stats", "-d", a.out, "-o", "train", "--output-format", "csv", "--"]))
+    for mode, prefix in runs[:1] if a.comm else runs:
         cmd = ["timeout", "-k", "10", str(a.limit)] + prefix + me + ["--child", mode]
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env)
         with open(os.path.join(a.out, "child_%s.log" % mode), "w") as f:
             f.write(p.stdout)
         if p.returncode != 0:                    # a fault, an abort or the time limit: nothing more is started on the GPU
@@ -182,6 +212,9 @@ def main():
             return 1
         line = [l for l in p.stdout.splitlines() if l.startswith("TRAIN_PROBE ")]
         result[mode] = json.loads(line[-1][len("TRAIN_PROBE "):]) if line else None
+    if a.comm:
+        print(json.dumps(dict(probe="train", timed=result["time"])))
+        return 0
     print(json.dumps(dict(probe="train", timed=result["time"], traced_step_ms=(result["trace"] or {}).get("step_ms_events"), slowest_kernels=slowest_kernels(a.out),
                           deterministic_share=deterministic_share(a.out) if a.deterministic else None)))
     return 0
