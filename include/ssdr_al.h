@@ -751,6 +751,27 @@ int ssdr_scatter_add_rows_dev(const int32_t* d_idx, int B, int rows_per_b, int s
 int ssdr_pool_grad_rows_dev(const float* d_src, float* d_dsrc, int lds, int src_rows, const int32_t* d_idx, int B, int m_per_b, int C,
                             const float* d_out, const float* d_dout, int ldo, void* stream);
 
+/* The training step's three launchers as stand-alone pieces (csrc/randla_train.hip); scratch per stream, enqueue only.  The tape of a step and
+ * these pieces call the same launch functions: the tile choice (16x16, 256x16, 16x256, 64x64 by M and N), the dW split over rows and the reductions'
+ * row chunks are the step's own.  All float32 with float32 accumulation.
+ * ssdr_randla_train_gemm_dev: C[i crs + j ccs] (+)= sum_k A[i ars + k acs] B[k brs + j bcs] (+ bias[j]) for i < M, j < N, k < K, one fmaf chain
+ *   over k from +0; `accumulate` != 0 adds to C's old value, otherwise C is overwritten.  Nothing outside those M x N elements is written.
+ * ssdr_randla_train_dw_dev: dW[i rs + j cs] = sum_r x[r ldx + i] dz[r out + j] for i < in, j < out over r < M (dz dense [M, out]); the rows are
+ *   split into slabs of a multiple of 16 rows (one per 512 rows, at most 1024, at most what 2^23 floats of [in][out] slabs hold), one fmaf chain
+ *   per slab, the slabs added in order from +0.
+ * ssdr_randla_train_reduce_dev: per channel c < C over the M rows of z (leading dimension ldz), in row chunks merged in order:
+ *   mode 0: out0 = mean, out1 = 1 / sqrt(biased variance + 1e-6) (chunk means and squared deviations, Chan's merge); with d_mov_mean / d_mov_var
+ *     (both or neither): moving -= (moving - x) * 0.01, x the mean and the variance (times M / (M - 1) when unbiased != 0 and M > 1).
+ *   mode 1: out0 = sum dY, out1 = sum dY (z - mean[c]) invstd[c], dY = da[r lda + c], times 0.2 where act != 0 and not av[r lda + c] > 0.
+ *   mode 2: out0 = sum z (out1 unused).
+ * Refused (SSDR_ERR_INVALID): NULL pointers, sizes <= 0, a leading dimension below its width, in * out > 2^23. */
+int ssdr_randla_train_gemm_dev(const float* d_A, int64_t ars, int64_t acs, const float* d_B, int64_t brs, int64_t bcs, float* d_C, int64_t crs, int64_t ccs,
+                               int M, int N, int K, const float* d_bias, int accumulate, void* stream);
+int ssdr_randla_train_dw_dev(const float* d_x, int ldx, const float* d_dz, int M, int in, int out, float* d_dW, int64_t rs, int64_t cs, void* stream);
+int ssdr_randla_train_reduce_dev(int mode, const float* d_z, int ldz, const float* d_da, const float* d_av, int lda, int act, const float* d_mean,
+                                 const float* d_invstd, int M, int C, float* d_out0, float* d_out1, float* d_mov_mean, float* d_mov_var, int unbiased,
+                                 void* stream);
+
 /* ---- data-parallel training: one process per GPU, every rank a replica (csrc/train_exchange.hip, DESIGN section 21 "Data-parallel") ----
  * The library links no collective library.  With an exchange set, _step_dev, _grads_dev and _forward_dev(is_training = 1) call `fn` where the ranks
  * must meet; `fn` only ENQUEUES the collective on `stream` (the call's stream) and returns 0, the host reads no device value.  The step is then the

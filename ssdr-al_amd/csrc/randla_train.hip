@@ -451,6 +451,7 @@ struct View { float* v = nullptr; float* g = nullptr; int ld = 0, w = 0; };
 View cols(const View& a, int c0, int w) { View r = a; r.v += c0; if (r.g) r.g += c0; r.w = w; return r; }
 
 struct TrainStatus { DevBuf word; };
+struct TrainPieces { DevBuf part, dwp; };      // scratch of the stand-alone launcher pieces, per stream
 
 struct Train {
     int L = 5, K = 16, C = 13, in_dim = 6;
@@ -522,6 +523,60 @@ void build_units(Train& m) {
 
 inline unsigned blocks_for(long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
+// ---- the launchers: the tape (Runner) and the stand-alone pieces ssdr_randla_train_{gemm, dw, reduce}_dev both go through these, so a piece runs
+// the step's own tile choice, split and chunk rules ----
+int launch_gemm(hipStream_t s, const float* A, long ars, long acs, const float* B, long brs, long bcs, float* Cp, long crs, long ccs, int M, int N, int K,
+                const float* bias, bool accumulate, int split = 1, long czs = 0) {
+    GemmArgs a{A, ars, acs, B, brs, bcs, Cp, crs, ccs, czs, M, N, K, 0, bias, accumulate ? 1 : 0};
+    a.kchunk = ((K + split - 1) / split + BK - 1) / BK * BK;
+    const unsigned z = (unsigned)((K + a.kchunk - 1) / a.kchunk);
+    if (M <= 16 && N <= 16) hipLaunchKernelGGL((gemm_kernel<16, 16, 1, 1>), dim3(1, 1, z), dim3(256), 0, s, a);
+    else if (N <= 16) hipLaunchKernelGGL((gemm_kernel<256, 16, 4, 4>), dim3(blocks_for(M, 256), 1, z), dim3(256), 0, s, a);
+    else if (M <= 16) hipLaunchKernelGGL((gemm_kernel<16, 256, 4, 4>), dim3(1, blocks_for(N, 256), z), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gemm_kernel<64, 64, 4, 4>), dim3(blocks_for(M, 64), blocks_for(N, 64), z), dim3(256), 0, s, a);
+    SSDR_HIP(hipGetLastError());
+    return SSDR_OK;
+}
+
+// the split of dW = x^T dz over its M rows: at most one slab per 512 rows, 1024 slabs, and what the slab buffer [split][in][out] holds
+struct DwSplit { long split; int kchunk, nz; };
+DwSplit dw_split(int M, int in, int out) {
+    long split = std::max<long>(1, std::min<long>(M / 512, 1024));
+    split = std::max<long>(1, std::min<long>(split, DWP_FLOATS / ((long)in * out)));
+    const int kchunk = (int)(((M + split - 1) / split + BK - 1) / BK * BK);
+    return DwSplit{split, kchunk, (M + kchunk - 1) / kchunk};
+}
+// dW[i * rs + j * cs] = sum over the M rows of x[r, i] dz[r, j]: slabs [nz][in][out] into dwp, then the combine.  dz is dense [M, out]
+int launch_dw(hipStream_t s, const float* x, int ldx, const float* dz, int M, int in, int out, float* dwp, float* dW, long rs, long cs) {
+    const DwSplit d = dw_split(M, in, out);
+    SSDR_TRY(launch_gemm(s, x, 1, ldx, dz, out, 1, dwp, out, 1, in, out, M, nullptr, false, (int)d.split, (long)in * out));
+    hipLaunchKernelGGL(sum_slabs_kernel, dim3(blocks_for((long)in * out)), dim3(256), 0, s, dwp, d.nz, in, out, dW, rs, cs);
+    SSDR_HIP(hipGetLastError());
+    return SSDR_OK;
+}
+
+// the row chunks of a per-channel reduction: about one per 1024 rows, at most 1024, and what the partial buffer [nchunks][2][C] holds
+struct RedSplit { int ct, chunk, nchunks; };
+RedSplit red_split(int M, int C) {
+    int ct = 8; while (ct < 64 && ct < C) ct *= 2;
+    long want = std::max<long>(1, std::min<long>(M / 1024, 1024));
+    want = std::max<long>(1, std::min<long>(want, PART_FLOATS / (2L * C)));
+    const int chunk = (int)((M + want - 1) / want);
+    return RedSplit{ct, chunk, (M + chunk - 1) / chunk};
+}
+// fills a.ct, a.chunk and a.part, launches the chunks; the number of chunks comes back
+template <int MODE> int launch_reduce_chunks(hipStream_t s, RedArgs& a, float* part) {
+    const RedSplit r = red_split(a.M, a.C);
+    a.ct = r.ct; a.chunk = r.chunk; a.part = part;
+    hipLaunchKernelGGL((reduce_kernel<MODE>), dim3(r.nchunks, blocks_for(a.C, r.ct)), dim3(256), 0, s, a);
+    return r.nchunks;
+}
+template <int MODE> int launch_combine(hipStream_t s, const RedArgs& a, int nchunks, float* out0, float* out1, float* mm, float* mv, int unbiased) {
+    hipLaunchKernelGGL((combine_kernel<MODE>), dim3(blocks_for(a.C, 64)), dim3(64), 0, s, a.part, nchunks, a.chunk, a.M, a.C, out0, out1, mm, mv, unbiased);
+    SSDR_HIP(hipGetLastError());
+    return SSDR_OK;
+}
+
 // One pass over the graph.  dry: only the workspace layout is computed (no launch).
 struct Runner {
     Train& m; hipStream_t s; bool dry; bool training; bool update_stats; bool want_grad;
@@ -540,17 +595,9 @@ struct Runner {
     void push(std::function<int()> f) { if (!dry && want_grad) tape.push_back(std::move(f)); }
 
     int gemm(const float* A, long ars, long acs, const float* B, long brs, long bcs, float* Cp, long crs, long ccs, int M, int N, int K, const float* bias,
-             bool accumulate, int split = 1, long czs = 0) {
+             bool accumulate) {
         if (dry) return SSDR_OK;
-        GemmArgs a{A, ars, acs, B, brs, bcs, Cp, crs, ccs, czs, M, N, K, 0, bias, accumulate ? 1 : 0};
-        a.kchunk = ((K + split - 1) / split + BK - 1) / BK * BK;
-        const unsigned z = (unsigned)((K + a.kchunk - 1) / a.kchunk);
-        if (M <= 16 && N <= 16) hipLaunchKernelGGL((gemm_kernel<16, 16, 1, 1>), dim3(1, 1, z), dim3(256), 0, s, a);
-        else if (N <= 16) hipLaunchKernelGGL((gemm_kernel<256, 16, 4, 4>), dim3(blocks_for(M, 256), 1, z), dim3(256), 0, s, a);
-        else if (M <= 16) hipLaunchKernelGGL((gemm_kernel<16, 256, 4, 4>), dim3(1, blocks_for(N, 256), z), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((gemm_kernel<64, 64, 4, 4>), dim3(blocks_for(M, 64), blocks_for(N, 64), z), dim3(256), 0, s, a);
-        SSDR_HIP(hipGetLastError());
-        return SSDR_OK;
+        return launch_gemm(s, A, ars, acs, B, brs, bcs, Cp, crs, ccs, M, N, K, bias, accumulate);
     }
     // W(k, n) of a unit: [in, out], or [out, in] for the transposed kernels
     static long w_rs(const Unit& u) { return u.transposed ? 1 : u.out; }
@@ -565,13 +612,7 @@ struct Runner {
     // RED_STATS: out0 = mean, out1 = 1 / std, and the row count behind them.  RED_BNBWD: out0 = dbeta, out1 = dgamma with out1 + C == out0.
     template <int MODE> int reduce(RedArgs a, float* out0, float* out1, float* mm, float* mv, int unbiased) {
         if (dry) return SSDR_OK;
-        int ct = 8; while (ct < 64 && ct < a.C) ct *= 2;
-        long want = std::max<long>(1, std::min<long>(a.M / 1024, 1024));
-        want = std::max<long>(1, std::min<long>(want, PART_FLOATS / (2L * a.C)));
-        a.ct = ct; a.chunk = (int)((a.M + want - 1) / want);
-        const int nchunks = (a.M + a.chunk - 1) / a.chunk;
-        a.part = m.part.as<float>();
-        hipLaunchKernelGGL((reduce_kernel<MODE>), dim3(nchunks, blocks_for(a.C, ct)), dim3(256), 0, s, a);
+        const int nchunks = launch_reduce_chunks<MODE>(s, a, m.part.as<float>());
         if (MODE != RED_SUM && meets()) {
             // one launch in front of the collective (the chunks' combine, into the send buffer), one behind it (the ranks' merge)
             float* send = m.xsend.as<float>(); float* recv = m.xrecv.as<float>();
@@ -585,9 +626,7 @@ struct Runner {
             SSDR_TRY(exchange(SSDR_XCHG_GATHER, send, recv, (size_t)2 * a.C));
             return xchg_merge_sums(recv, m.xg.world, 2 * a.C, out1, s);
         }
-        hipLaunchKernelGGL((combine_kernel<MODE>), dim3(blocks_for(a.C, 64)), dim3(64), 0, s, a.part, nchunks, a.chunk, a.M, a.C, out0, out1, mm, mv, unbiased);
-        SSDR_HIP(hipGetLastError());
-        return SSDR_OK;
+        return launch_combine<MODE>(s, a, nchunks, out0, out1, mm, mv, unbiased);
     }
 
     // z [M, out] = x W + b; with a batch norm its statistics land in BS (batch, or moving in inference mode)
@@ -611,13 +650,7 @@ struct Runner {
     int linear_bwd(int ui, const View& x, int M, float* dz) {
         const Unit& u = m.units[ui];
         if (u.bias) { RedArgs r{}; r.z = dz; r.ldz = u.out; r.M = M; r.C = u.out; SSDR_TRY(reduce<RED_SUM>(r, m.grd(u.ob), nullptr, nullptr, nullptr, 0)); }
-        // dW = x^T dz: the rows are split over workgroups, slabs [split][in][out], then the combine
-        long split = std::max<long>(1, std::min<long>(M / 512, 1024));
-        split = std::max<long>(1, std::min<long>(split, DWP_FLOATS / ((long)u.in * u.out)));
-        const int kchunk = (int)(((M + split - 1) / split + BK - 1) / BK * BK);
-        const int nz = (M + kchunk - 1) / kchunk;
-        SSDR_TRY(gemm(x.v, 1, x.ld, dz, u.out, 1, m.dwp.as<float>(), u.out, 1, u.in, u.out, M, nullptr, false, (int)split, (long)u.in * u.out));
-        hipLaunchKernelGGL(sum_slabs_kernel, dim3(blocks_for((long)u.in * u.out)), dim3(256), 0, s, m.dwp.as<float>(), nz, u.in, u.out, m.grd(u.oW), w_rs(u), w_cs(u));
+        SSDR_TRY(launch_dw(s, x.v, x.ld, dz, M, u.in, u.out, m.dwp.as<float>(), m.grd(u.oW), w_rs(u), w_cs(u)));
         if (x.g) SSDR_TRY(gemm(dz, u.out, 1, m.par(u.oW), w_cs(u), w_rs(u), x.g, x.ld, 1, M, u.in, u.out, nullptr, true));       // dx += dz W^T
         SSDR_HIP(hipGetLastError());
         return SSDR_OK;
@@ -1162,6 +1195,50 @@ int ssdr_randla_train_export(void* handle, void* net) {
     }
     for (int l = 1 + 8 * m->L; l < 1 + 8 * m->L + 1 + m->L + 3; ++l) { fold(l + m->L, W, b); SSDR_TRY(put(l, W, b, true)); }
     return SSDR_OK;
+}
+
+/* ---- the launchers as stand-alone pieces (include/ssdr_al.h): the tile choice, the dW split and the reduction chunks are the step's own ---- */
+int ssdr_randla_train_gemm_dev(const float* d_A, int64_t ars, int64_t acs, const float* d_B, int64_t brs, int64_t bcs, float* d_C, int64_t crs, int64_t ccs,
+                               int M, int N, int K, const float* d_bias, int accumulate, void* stream) {
+    if (!d_A || !d_B || !d_C) { set_error("randla_train_gemm: NULL pointer"); return SSDR_ERR_INVALID; }
+    if (M <= 0 || N <= 0 || K <= 0) { set_error("randla_train_gemm: M = %d, N = %d, K = %d must be positive", M, N, K); return SSDR_ERR_INVALID; }
+    SSDR_TRY(ensure_init());
+    return launch_gemm(pick_stream(stream), d_A, (long)ars, (long)acs, d_B, (long)brs, (long)bcs, d_C, (long)crs, (long)ccs, M, N, K, d_bias, accumulate != 0);
+}
+
+int ssdr_randla_train_dw_dev(const float* d_x, int ldx, const float* d_dz, int M, int in, int out, float* d_dW, int64_t rs, int64_t cs, void* stream) {
+    if (!d_x || !d_dz || !d_dW) { set_error("randla_train_dw: NULL pointer"); return SSDR_ERR_INVALID; }
+    if (M <= 0 || in <= 0 || out <= 0) { set_error("randla_train_dw: M = %d, in = %d, out = %d must be positive", M, in, out); return SSDR_ERR_INVALID; }
+    if (ldx < in) { set_error("randla_train_dw: the leading dimension %d is below in = %d", ldx, in); return SSDR_ERR_INVALID; }
+    if ((long)in * out > DWP_FLOATS) { set_error("randla_train_dw: in * out = %ld is more than one slab holds", (long)in * out); return SSDR_ERR_INVALID; }
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream);
+    TrainPieces& sc = per_stream<TrainPieces>(s);
+    SSDR_TRY(sc.dwp.reserve(sizeof(float) * (size_t)dw_split(M, in, out).nz * (size_t)in * (size_t)out));
+    return launch_dw(s, d_x, ldx, d_dz, M, in, out, sc.dwp.as<float>(), d_dW, (long)rs, (long)cs);
+}
+
+/* mode 0: d_out0 = mean, d_out1 = 1 / sqrt(biased variance + 1e-6) of z's columns, and the moving averages when both are given.
+ * mode 1: d_out0 = sum dY, d_out1 = sum dY xhat with dY = da (x 0.2 where act and not av > 0), xhat = (z - mean) invstd.   mode 2: d_out0 = sum z. */
+int ssdr_randla_train_reduce_dev(int mode, const float* d_z, int ldz, const float* d_da, const float* d_av, int lda, int act, const float* d_mean,
+                                 const float* d_invstd, int M, int C, float* d_out0, float* d_out1, float* d_mov_mean, float* d_mov_var, int unbiased,
+                                 void* stream) {
+    if (mode < RED_STATS || mode > RED_SUM) { set_error("randla_train_reduce: mode %d (0 statistics, 1 batch-norm backward, 2 sum)", mode); return SSDR_ERR_INVALID; }
+    if (!d_z || !d_out0 || (mode != RED_SUM && !d_out1)) { set_error("randla_train_reduce: NULL pointer"); return SSDR_ERR_INVALID; }
+    if (mode == RED_BNBWD && (!d_da || !d_mean || !d_invstd || (act && !d_av))) { set_error("randla_train_reduce: mode 1 needs da, mean, invstd (and av with act)"); return SSDR_ERR_INVALID; }
+    if ((d_mov_mean == nullptr) != (d_mov_var == nullptr)) { set_error("randla_train_reduce: the moving mean and variance come together"); return SSDR_ERR_INVALID; }
+    if (M <= 0 || C <= 0) { set_error("randla_train_reduce: M = %d, C = %d must be positive", M, C); return SSDR_ERR_INVALID; }
+    if (ldz < C || (mode == RED_BNBWD && lda < C)) { set_error("randla_train_reduce: a leading dimension is below C = %d", C); return SSDR_ERR_INVALID; }
+    if (2L * C > PART_FLOATS) { set_error("randla_train_reduce: C = %d is more than the partial buffer holds", C); return SSDR_ERR_INVALID; }
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream);
+    TrainPieces& sc = per_stream<TrainPieces>(s);
+    SSDR_TRY(sc.part.reserve(sizeof(float) * 2 * (size_t)C * (size_t)red_split(M, C).nchunks));
+    RedArgs a{}; a.z = d_z; a.ldz = ldz; a.da = d_da; a.av = d_av; a.lda = lda; a.act = act; a.mean = d_mean; a.invstd = d_invstd; a.M = M; a.C = C;
+    if (mode == RED_STATS) { const int n = launch_reduce_chunks<RED_STATS>(s, a, sc.part.as<float>()); return launch_combine<RED_STATS>(s, a, n, d_out0, d_out1, d_mov_mean, d_mov_var, unbiased); }
+    if (mode == RED_BNBWD) { const int n = launch_reduce_chunks<RED_BNBWD>(s, a, sc.part.as<float>()); return launch_combine<RED_BNBWD>(s, a, n, d_out0, d_out1, nullptr, nullptr, 0); }
+    const int n = launch_reduce_chunks<RED_SUM>(s, a, sc.part.as<float>());
+    return launch_combine<RED_SUM>(s, a, n, d_out0, nullptr, nullptr, nullptr, 0);
 }
 
 /* Waits for `stream`; the bits the training calls on it raised since the last call (bit 0: no valid row, loss and gradient are 0; bit 1: a label or pseudo

@@ -30,6 +30,12 @@ def union_case(flavour):
     """(cfg, weights, union batch [B = 3], dropout mask of the gradient call, class weights, ignored labels) of a flavour:
     s3dis (class weights), sem3d (label 0 ignored: the ranks' valid counts differ), novalid (sem3d with the LAST tile's labels all ignored),
     allinvalid (sem3d with every label ignored)"""
+    if flavour in TC.PATH_CASES:              # a case of tests/test_train_paths.py at B = 3: ranks with different row counts, none a power of two
+        cfg, kw, cw, ign = TC.PATH_CASES[flavour]
+        assert cfg.batch_size == UNION_B and cfg.num_classes == 13
+        seed = TC.SEEDS[flavour]
+        batch = TC.make_batch(cfg, seed, **kw)
+        return cfg, TC.weights_for(cfg, seed), batch, TC.make_mask(batch, seed), TC.CLASS_W13, ign
     base = "s3dis" if flavour == "s3dis" else "sem3d"
     seed = UNION_SEEDS[base]
     if base == "s3dis":

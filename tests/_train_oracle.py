@@ -35,9 +35,12 @@ class Graph:
         self.stats = {}        # scope -> (batch mean, biased batch variance, rows)
         self.signs = []        # pre-activation > 0 of every leaky ReLU
         self.ties = []         # per pooling: which of the 16 rows equal the maximum
+        self.pre = []          # the pre-activation of every leaky ReLU (for _train_cases.margins)
+        self.pooled = []       # per pooling: the 16 rows it takes the maximum of
 
     def lrelu(self, y):
         self.signs.append((y > 0).detach())
+        self.pre.append(y.detach())
         return torch.where(y > 0, y, y * LRELU)
 
     def linear(self, x, name):
@@ -102,6 +105,7 @@ def forward(g, batch, mask):
         # one_winner: torch.max(dim) sends a tied maximum's whole gradient to one row — what TF does NOT do; only there to show that the tests' bars notice
         samp = pooled.max(dim=2).values if g.one_winner else pooled.amax(dim=2)
         g.ties.append((pooled == samp[:, :, None, :]).detach())
+        g.pooled.append(pooled.detach())
         if i == 0:
             enc.append(out)
         enc.append(samp)
@@ -156,7 +160,7 @@ def run(weights, batch, mask, class_weights=None, ignored=(), dtype=torch.float6
     logits, f2 = forward(g, batch, mask)
     C = logits.shape[1]
     cw = np.ones(C) if class_weights is None else class_weights
-    out = {"logits": logits.detach().numpy(), "feat32": f2.detach().numpy(), "stats": g.stats, "signs": g.signs, "ties": g.ties, "P": P}
+    out = {"logits": logits.detach().numpy(), "feat32": f2.detach().numpy(), "stats": g.stats, "signs": g.signs, "ties": g.ties, "pre": g.pre, "pooled": g.pooled, "P": P}
     if "labels" in batch:
         loss, acc, n = loss_and_accuracy(logits, batch["labels"], batch["act"], batch["pse"], cw, ignored, C)
         out.update(loss=float(loss.detach()), acc=float(acc), valid=n)

@@ -180,18 +180,7 @@ def test_gradients(backend, case):
     G = tr.grads()
     assert tr.step_count() == 0
     B = batch["labels"].shape[0]
-    bad, rows = [], []
-    for (name, key), g in G.items():
-        g64, g32 = r64["grads"][(name, key)], r32["grads"][(name, key)]
-        assert g.shape == g64.shape and np.isfinite(g).all(), (name, key)
-        scale = np.abs(g64).max()
-        if key == "b" and (name, "gamma") in r64["grads"]:
-            scale = np.abs(r64["grads"][(name, "W")]).max()
-        m_dev, m_32 = np.abs(g - g64).max() / scale, np.abs(g32 - g64).max() / scale
-        bar = max(8 * m_32, 8 * U * np.sqrt(2.0 * TC.reduction_rows(cfg, B, name)))
-        rows.append("%-36s %-5s device %.2e float32-torch %.2e bar %.2e" % (name, key, m_dev, m_32, bar))
-        if not m_dev <= bar:
-            bad.append(rows[-1])
+    rows, bad, _ = TC.check_gradients(G, cfg, B, r64, r32)      # the loop, shared with tests/test_train_paths.py
     print("\n".join(rows))
     assert not bad, "\n".join(bad)
     after = tr.weights()

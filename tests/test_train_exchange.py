@@ -320,7 +320,8 @@ def _check_union(r, flavour, what):
     assert float((0.01 * var_.numpy() * (1.0 / (n / WK.UNION_B - 1) - 1.0 / (n - 1))).max()) > 10 * 4e-7
 
 
-@pytest.mark.parametrize("flavour,split,port", [("s3dis", "2,1", 29615), ("s3dis", "1,1,1", 29617), ("sem3d", "2,1", 29619), ("sem3d", "1,1,1", 29621)])
+@pytest.mark.parametrize("flavour,split,port", [("s3dis", "2,1", 29615), ("s3dis", "1,1,1", 29617), ("sem3d", "2,1", 29619), ("sem3d", "1,1,1", 29621),
+                                                ("b3n360", "2,1", 29631)])        # ragged row chunks in xchg_pack_stats, on ranks with different M
 def test_data_parallel_step_equals_the_union_step(tmp_path, emu_lib, flavour, split, port):
     world = len(split.split(","))
     r = _gloo(tmp_path, world, port, SSDR_TEST_PART="union", SSDR_TEST_FLAVOUR=flavour, SSDR_TEST_SPLIT=split)
