@@ -191,6 +191,21 @@ int ssdr_tile_select_batch_dev(const float* d_points, const float* d_colors, int
                                size_t num_clouds, const float* centers, size_t num_points, const int32_t* d_perm, const float* d_dup_u,
                                float color_scale, float* d_out_xyz, float* d_out_feat, int32_t* d_out_idx, const int32_t* d_labels,
                                int32_t* d_out_labels, void* stream);
+/* ssdr_grid_subsample_batch_dev + ssdr_tile_select_batch_dev in one call, for a caller that keeps nothing of the sub-sampled clouds but the tiles: the tiles
+ * (d_out_xyz / d_out_feat / d_out_labels) are those of the two calls bit for bit, with d_colors = the sub-sampled features and d_labels = the sub-sampled
+ * classes (ldim 1).  The partition path (SSDR_SUBSAMPLE_AUTO) reduces only the spatial buckets that can hold one of the num_points rows nearest to a cloud's
+ * centre: the bounds follow from the buckets' boxes, the sufficiency check from exact row counts, all on the stream and from this call's inputs alone.  d_sub_*
+ * then receive the rows of those buckets (ascending voxel key), d_sub_m[r] their count, and d_out_idx counts among them.  ssdr_grid_subsample_status reports
+ * as for the two calls (a refused cloud: repeat with SSDR_SUBSAMPLE_SORT, which produces every row). */
+int ssdr_tile_from_rooms_batch_dev(const float* d_points, const float* d_features, size_t fdim, const int32_t* d_classes, size_t ldim,
+                                   const int64_t* cloud_offsets, size_t num_clouds, float sampleDl,
+                                   float* d_sub_points, float* d_sub_features, int32_t* d_sub_classes, int64_t* d_sub_m,
+                                   const float* centers, size_t num_points, const int32_t* d_perm, const float* d_dup_u, float color_scale,
+                                   float* d_out_xyz, float* d_out_feat, int32_t* d_out_idx, int32_t* d_out_labels, void* stream);
+/* Per cloud of the last ssdr_tile_from_rooms_batch_dev on `stream` (waits for it; int32 [num_clouds] each, may be NULL): the stage the reduction ended in
+ * (1: the first stage's buckets sufficed or were the whole cloud, 2: the set estimated from the first stage's points per voxel sufficed, 3: the rest of the
+ * cloud was needed, 0: reduced whole without an order, -1: the sort), the buckets reduced, the cloud's non-empty buckets. */
+int ssdr_tile_from_rooms_stats(void* stream, int32_t* out_stage, int32_t* out_reduced, int32_t* out_buckets, size_t num_clouds);
 /* Test-time variant (S3/s3dis_dataset_test.py:105-143): the same tile, plus the possibility-map update
  * possibility[idx] += (1 - dists/max(dists))^2 over the tile's (un-padded) points (float64 map, float32 dists) and,
  * optionally, min / argmin of the updated map (the next pick: :106-108).  An empty cloud (*d_m <= 0): the tile outputs and the

@@ -103,7 +103,7 @@ __global__ __launch_bounds__(BS) void fe_params(FeTab t, const float* partial, f
     }
     block_minmax3(mn, mx, s_mm);
     if (threadIdx.x == 0) {
-        if (r == 0) { for (int i = 0; i < 8; ++i) counters[i] = 0; }          // [0] work items, [3] overflow rows
+        if (r == 0) { for (int i = 0; i < 64; ++i) counters[i] = 0; }         // [0] work items, [3] overflow rows; [32..56) the same per stage of the staged reduction
         GsParams p; FeGeom g;
         const float inv = 1 / dl;               // grid_subsampling.cpp:27-31
         float nd[3];
@@ -706,16 +706,240 @@ __global__ __launch_bounds__(BS) void fe_move(FeMoveArgs a) {
     }
 }
 
-struct FeState { DevBuf partial, geom, cntm, tot, boff, items, counters, rec, nocc, trow, lrc, pre, rowcnt, rcp; bool rcp_ready = false; };
+// ---- reduction of the buckets a tile can need only ------------------------------------------------------------------------------
+// The hot path keeps num_points rows of a room: the barycentres nearest to a picked centre (tile.hip).  A barycentre lies in its voxel, so the
+// least and greatest distance from the centre to a bucket's box bound every row the bucket can give BEFORE its records are read.  The room's
+// non-empty buckets are ordered by that least distance, and fe_reduce (the same kernel: it only sees shorter work lists) runs in stages:
+//   1  ranks [0, K1): K1 = the first rank at which the cumulative POINTS reach 6 num_points, widened to every rank whose least distance does not
+//      exceed the greatest distance of a rank below it.  Enough for rooms of up to ~5 raw points per occupied voxel (S3DIS-like rooms at a 4 cm
+//      grid hold 4 to 5), and it measures rho = points per occupied voxel around the centre exactly
+//   check (after every stage): D = least distance of the first unreduced rank; the buckets whose greatest distance is below D hold exact row counts by
+//      now.  At least num_points of them: every row of an unreduced bucket is strictly farther than num_points reduced rows and can neither enter
+//      the tile nor tie with its last row: done.  Otherwise
+//   2  ranks [K1, K2): K2 = the first rank at which the cumulative points reach 1.15 rho num_points, widened in the same way; if the check fails again
+//   3  ranks [K2, n): the rest of the room (also what a room of fewer than num_points voxels ends with: the tile's padding branch).
+// Unreduced buckets read as empty (nocc, lrc = 0) to fe_rowpre / fe_move: the rows that exist keep their key order, so the tile's tie rule
+// (distance, then row) is the same relation on them.  Nothing is kept between calls; the set of reduced buckets is a function of the inputs.
+constexpr int FE_TO_NMAX = 8192;     // non-empty buckets of a room the order is sorted for (one LDS word each); a room with more is reduced whole
+constexpr int FE_TO_KBITS = 14;      // low bits of a sort word: the bucket (FE_NBMAX = 2^14); above them 18 bits of the least distance's pattern
+static_assert(FE_NBMAX == 1 << FE_TO_KBITS, "bucket bits of the order's sort words");
+struct FeCentres { float c[3 * RADIX_MAX_SEG]; };
+struct FeTileInfo { int n, k1, k2, stage, reduced, pad0, pad1, pad2; };      // stage: 0 = reduced whole without an order, 1..3 = the stage that was the last
+struct FeTileArgs {
+    FeTab t; FeCentres cen; const FeGeom* geom; const unsigned* tot; const unsigned* boff; unsigned* nocc; unsigned char* lrc;
+    unsigned* okey; float* odmax; unsigned* ocum; FeItem* work; int* counters; FeTileInfo* info; int num_points, k1_mult, k1_widen;
+};
+// per stage s = 1..3 a block of 8 counters behind the whole-room ones: [0] items of the stage's work list, [3] the overflow rows' cursor
+__host__ __device__ __forceinline__ int* fe_stage_counters(int* counters, int stage) { return counters + 32 + 8 * (stage - 1); }
+
+// Least and greatest squared distance from c to any barycentre of bucket b, safe against rounding on both sides:
+//  - the box: voxels [i0, i1) per axis (clipped to the grid), org + i dl, taken in double (its own rounding is 2^-53 of a coordinate);
+//  - a barycentre's distance from its voxel: the voxel test is floorf((p - org) / dl) in fp32 (two roundings, each <= u |p| with u = 2^-24), and a position sum is a
+//    sequential fp32 sum of k <= FE_CAP terms times the rounded (float)(1 / k): |computed - mean| <= (k + 1) u max|p| to first order.  The margin takes
+//    (FE_CAP + 8) 2 u A with A = the grid's largest |coordinate| (twice the first-order bound), and no less than dl / 4;
+//  - tile_dist: (dx dx + dy dy) + dz dz in fp32 is five roundings deep per term (the difference, the square, two sums: all terms >= 0), so the
+//    computed value lies within (1 +- u)^5 of the exact one: the bounds are scaled by 1 -+ 2^-20 = 16 u (the conversion to float costs one more u).
+//    A least distance below 1e-30 counts as 0 (squares that underflow).
+__device__ __forceinline__ void fe_bucket_bounds(const FeGeom& g, int b, const float* c, float& dmin2, float& dmax2) {
+    const int bx = b % g.nbx, by = (b / g.nbx) % g.nby, bz = b / (g.nbx * g.nby);
+    const int nd[3] = {g.nx, g.ny, g.nz};
+    const int i0[3] = {bx << g.sx, by << 3, bz << 3};
+    const int i1[3] = {min((bx + 1) << g.sx, g.nx), min((by + 1) << 3, g.ny), min((bz + 1) << 3, g.nz)};
+    const double dl = (double)g.dl;
+    double amax = 0.0;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) amax = fmax(amax, fmax(fabs((double)g.org[d]), fabs((double)g.org[d] + (double)(nd[d] + 1) * dl)));
+    const double margin = fmax(0.25 * dl, (double)(FE_CAP + 8) * (1.0 / 8388608.0) * amax);
+    double lo2 = 0.0, hi2 = 0.0;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const double lo = (double)g.org[d] + (double)i0[d] * dl - margin, hi = (double)g.org[d] + (double)i1[d] * dl + margin, cd = (double)c[d];
+        const double nearest = fmax(fmax(lo - cd, cd - hi), 0.0), farthest = fmax(fabs(cd - lo), fabs(hi - cd));
+        lo2 += nearest * nearest; hi2 += farthest * farthest;
+    }
+    dmin2 = lo2 < 1.0e-30 ? 0.f : (float)(lo2 * (1.0 - 1.0 / 1048576.0));
+    dmax2 = (float)(hi2 * (1.0 + 1.0 / 1048576.0));
+}
+__device__ __forceinline__ FeItem fe_tile_item(const FeTileArgs& a, const FeGeom& g, int r, int b) {
+    FeItem it; it.base = (unsigned)a.t.off[r] + a.boff[(size_t)r * (FE_NBMAX + 1) + b]; it.n = a.tot[(size_t)r * FE_NBMAX + b];
+    it.rb = ((unsigned)r << 16) | (unsigned)b; it.sx = (unsigned)g.sx;
+    it.org[0] = g.org[0]; it.org[1] = g.org[1]; it.org[2] = g.org[2]; it.dl = g.dl;
+    return it;
+}
+
+// One workgroup per room, after fe_bscan: every non-empty bucket reads as empty to the row kernels until a stage reduces it; the room's buckets by
+// ascending least distance (sort word = 18 bits of the distance's pattern, rounded DOWN: still a lower bound | bucket: no two words are equal, the
+// order is the inputs'), their greatest distances and running point counts in that order; stage 1's work items.
+__global__ __launch_bounds__(FE_NT) void fe_tile_order(FeTileArgs a) {
+    __shared__ unsigned s_k[FE_TO_NMAX];
+    __shared__ unsigned s_m;
+    __shared__ unsigned long long s_w[FE_NT / 64];
+    __shared__ int s_n, s_k1, s_base;
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const FeGeom g = a.geom[r];
+    int* cb = fe_stage_counters(a.counters, 1);
+    FeTileInfo ti; ti.n = 0; ti.k1 = 0; ti.k2 = 0; ti.stage = 0; ti.reduced = 0; ti.pad0 = ti.pad1 = ti.pad2 = 0;
+    if (!g.ok) { if (tid == 0) a.info[r] = ti; return; }
+    const float* c = a.cen.c + 3 * r;
+    const unsigned* tot = a.tot + (size_t)r * FE_NBMAX;
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    for (int b = tid; b < g.nb; b += FE_NT) {
+        if (!tot[b]) continue;
+        const size_t tb = (size_t)r * FE_NBMAX + b;
+        a.nocc[tb] = 0u;
+        uint4* z = reinterpret_cast<uint4*>(a.lrc + tb * FE_LR);
+#pragma unroll
+        for (int q = 0; q < FE_LR / 16; ++q) z[q] = make_uint4(0u, 0u, 0u, 0u);
+        float dmin2, dmax2;
+        fe_bucket_bounds(g, b, c, dmin2, dmax2);
+        const int at = atomicAdd(&s_n, 1);
+        if (at < FE_TO_NMAX) s_k[at] = (((__float_as_uint(dmin2) & 0x7fffffffu) >> 13) << FE_TO_KBITS) | (unsigned)b;
+    }
+    __syncthreads();
+    const int n = s_n;
+    __syncthreads();
+    ti.n = n; ti.k1 = n; ti.k2 = n; ti.reduced = n;
+    if (n > FE_TO_NMAX) {          // no order: the whole room in stage 1
+        if (tid == 0) { s_base = atomicAdd(&cb[0], n); s_n = 0; }
+        __syncthreads();
+        for (int b = tid; b < g.nb; b += FE_NT) if (tot[b]) a.work[(size_t)s_base + atomicAdd(&s_n, 1)] = fe_tile_item(a, g, r, b);
+        if (tid == 0) a.info[r] = ti;
+        return;
+    }
+    // bitonic network over the next power of two (the padding sorts last); a rank-by-counting pass was tried: n^2 comparisons on ONE compute unit, 347 us
+    // against this network's 50 us for the ~1500 buckets of a room
+    int N2 = 2; while (N2 < n) N2 <<= 1;
+    for (int i = n + tid; i < N2; i += FE_NT) s_k[i] = 0xffffffffu;
+    if (tid == 0) s_k1 = n;
+    __syncthreads();
+    for (int k = 2; k <= N2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < N2 / 2; i += FE_NT) {
+                const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo | j;
+                const unsigned x = s_k[lo], y = s_k[hi];
+                if ((x > y) == !(lo & k)) { s_k[lo] = y; s_k[hi] = x; }
+            }
+            __syncthreads();
+        }
+    }
+    const unsigned long long want = (unsigned long long)a.k1_mult * (unsigned long long)a.num_points;
+    unsigned long long carry = 0;
+    for (int i0 = 0; i0 < n; i0 += FE_NT) {
+        const int i = i0 + tid;
+        const int b = i < n ? (int)(s_k[i] & (FE_NBMAX - 1)) : 0;
+        const unsigned long long pts = i < n ? tot[b] : 0u;
+        unsigned long long total;
+        const unsigned long long incl = carry + fe_block_scan(pts, s_w, FE_NT, total) + pts;
+        if (i < n) {
+            float dmin2, dmax2;
+            fe_bucket_bounds(g, b, c, dmin2, dmax2);
+            a.okey[(size_t)r * FE_NBMAX + i] = s_k[i]; a.odmax[(size_t)r * FE_NBMAX + i] = dmax2; a.ocum[(size_t)r * FE_NBMAX + i] = (unsigned)incl;
+            if (incl - pts < want && incl >= want) s_k1 = i + 1;
+        }
+        carry += total;
+    }
+    __syncthreads();
+    int k1 = s_k1;
+    if (a.k1_widen && k1 < n) {          // every rank whose least distance does not exceed the greatest distance of a rank below k1: stage 1 can then pass the check itself
+        if (tid == 0) s_m = 0u;
+        __syncthreads();
+        for (int i = tid; i < k1; i += FE_NT) {
+            float dmin2, dmax2;
+            fe_bucket_bounds(g, (int)(s_k[i] & (FE_NBMAX - 1)), c, dmin2, dmax2);
+            atomicMax(&s_m, __float_as_uint(dmax2));
+        }
+        __syncthreads();
+        const unsigned mq = s_m >> 13;
+        unsigned long long v = 0, total;
+        for (int i = tid; i < n; i += FE_NT) v += (s_k[i] >> FE_TO_KBITS) <= mq ? 1u : 0u;
+        fe_block_scan(v, s_w, FE_NT, total);
+        k1 = min(n, max((int)total, k1));
+    }
+    if (tid == 0) s_base = k1 ? atomicAdd(&cb[0], k1) : 0;
+    __syncthreads();
+    for (int i = tid; i < k1; i += FE_NT) a.work[(size_t)s_base + i] = fe_tile_item(a, g, r, (int)(s_k[i] & (FE_NBMAX - 1)));
+    ti.k1 = k1; ti.k2 = k1; ti.reduced = k1; ti.stage = 1;
+    if (tid == 0) a.info[r] = ti;
+}
+
+// One workgroup per room between two stages: what the stage before left (exact row counts in nocc) decides the next stage's ranks.
+template <int STAGE>
+__global__ __launch_bounds__(FE_NT) void fe_tile_plan(FeTileArgs a) {
+    __shared__ unsigned long long s_w[FE_NT / 64];
+    __shared__ unsigned s_u[2];
+    __shared__ int s_base;
+    const int r = blockIdx.x, tid = threadIdx.x;
+    int* cb = fe_stage_counters(a.counters, STAGE);
+    if (r == 0 && tid == 0) cb[3] = fe_stage_counters(a.counters, STAGE - 1)[3];          // the overflow rows go on where the stage before stopped
+    const FeTileInfo ti = a.info[r];
+    const int n = ti.n, k1 = ti.k1;
+    if (k1 >= n) return;           // the room was reduced whole by stage 1 (or has no bucket)
+    const unsigned* key = a.okey + (size_t)r * FE_NBMAX;
+    const float* dmax = a.odmax + (size_t)r * FE_NBMAX;
+    const unsigned* cum = a.ocum + (size_t)r * FE_NBMAX;
+    const unsigned* nocc = a.nocc + (size_t)r * FE_NBMAX;
+    int lo, hi;
+    unsigned long long total;
+    if (STAGE == 2) {
+        // stage 1's ranks suffice when the room holds few enough points per voxel
+        const float D1 = __uint_as_float((key[k1] >> FE_TO_KBITS) << 13);
+        unsigned long long v = 0;
+        for (int i = tid; i < k1; i += FE_NT) if (dmax[i] < D1) v += nocc[key[i] & (FE_NBMAX - 1)];
+        fe_block_scan(v, s_w, FE_NT, total);
+        if (total >= (unsigned long long)a.num_points) return;
+        v = 0;
+        for (int i = tid; i < k1; i += FE_NT) v += nocc[key[i] & (FE_NBMAX - 1)];
+        fe_block_scan(v, s_w, FE_NT, total);
+        // points of the ranks that are expected to hold 1.15 num_points occupied voxels at stage 1's points per voxel
+        const double target = total ? 1.15 * (double)cum[k1 - 1] / (double)total * (double)a.num_points : 4.0e9;
+        const unsigned tgt = target >= 4.0e9 ? 0xffffffffu : (unsigned)target + 1u;
+        if (tid == 0) { s_u[0] = (unsigned)n; s_u[1] = 0u; }
+        __syncthreads();
+        for (int i = tid; i < n; i += FE_NT) if ((i ? cum[i - 1] : 0u) < tgt && cum[i] >= tgt) s_u[0] = (unsigned)(i + 1);
+        __syncthreads();
+        const int k2a = max((int)s_u[0], k1);
+        for (int i = tid; i < k2a; i += FE_NT) atomicMax(&s_u[1], __float_as_uint(dmax[i]));          // (patterns of non-negative floats; a NaN's is above all: everything)
+        __syncthreads();
+        const unsigned mq = s_u[1] >> 13;
+        v = 0;
+        for (int i = tid; i < n; i += FE_NT) v += (key[i] >> FE_TO_KBITS) <= mq ? 1u : 0u;         // ranks whose least distance does not exceed that greatest one (a prefix: the order)
+        fe_block_scan(v, s_w, FE_NT, total);
+        lo = k1; hi = min(n, max((int)total, k2a));
+        if (tid == 0) { a.info[r].k2 = hi; a.info[r].reduced = hi; a.info[r].stage = 2; }
+    } else {
+        const int k2 = ti.k2;
+        if (k2 >= n) return;
+        const float D = __uint_as_float((key[k2] >> FE_TO_KBITS) << 13);
+        unsigned long long v = 0;
+        for (int i = tid; i < k2; i += FE_NT) if (dmax[i] < D) v += nocc[key[i] & (FE_NBMAX - 1)];
+        fe_block_scan(v, s_w, FE_NT, total);
+        if (total >= (unsigned long long)a.num_points) return;
+        lo = k2; hi = n;
+        if (tid == 0) { a.info[r].reduced = n; a.info[r].stage = 3; }
+    }
+    if (tid == 0) s_base = hi > lo ? atomicAdd(&cb[0], hi - lo) : 0;
+    __syncthreads();
+    const FeGeom g = a.geom[r];
+    for (int i = lo + tid; i < hi; i += FE_NT) a.work[(size_t)s_base + (i - lo)] = fe_tile_item(a, g, r, (int)(key[i] & (FE_NBMAX - 1)));
+}
+
+struct FeState {
+    DevBuf partial, geom, cntm, tot, boff, items, counters, rec, nocc, trow, lrc, pre, rowcnt, rcp; bool rcp_ready = false;
+    DevBuf okey, odmax, ocum, work, tinfo; int tile_clouds = 0;          // the staged reduction's tables; rooms of the last call if it was staged
+};
 
 }  // namespace
 
 bool frontend_fits(size_t fdim, size_t ldim) { return 3 + fdim + ldim <= 7; }
 
 // All clouds of a batch in the same launches; prm: the caller's per-cloud GsParams (status / voxel count as the sort-based path leaves them).
+// centres (host [nr, 3]) / num_points: reduce only the buckets the num_points rows nearest to every room's centre can lie in (the staged reduction above);
+// the outputs then hold those buckets' rows, in key order, and d_om their count.  centres NULL: every bucket.
 int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const int32_t* d_c, size_t ldim, const int64_t* room_off, size_t nr, float dl,
-                          float* d_op, float* d_of, int32_t* d_oc, int64_t* d_om, GsParams* prm, hipStream_t s) {
+                          float* d_op, float* d_of, int32_t* d_oc, int64_t* d_om, GsParams* prm, hipStream_t s, const float* centres, size_t num_points) {
     FeState& S = per_stream<FeState>(s);
+    S.tile_clouds = 0;
     FeTab t; t.nr = (int)nr;
     int maxn = 0;
     for (size_t r = 0; r < nr; ++r) {
@@ -770,7 +994,33 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
     ra.nocc = S.nocc.as<unsigned>(); ra.trow = S.trow.as<unsigned>(); ra.lrc = S.lrc.as<unsigned char>(); ra.fdim = (int)fdim; ra.ldim = (int)ldim;
     {
     ProfScope prof("fe_reduce", s, 0.0);
-    if (!fe_image) {
+    if (centres && !fe_image) {
+        // the same kernel per stage, over the stage's work list; the lists' lengths are the device's (workgroups beyond them exit at once)
+        SSDR_TRY(S.okey.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.odmax.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.ocum.reserve(4 * (size_t)FE_NBMAX * nr));
+        SSDR_TRY(S.work.reserve(sizeof(FeItem) * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.tinfo.reserve(sizeof(FeTileInfo) * RADIX_MAX_SEG));
+        FeTileArgs ta; ta.t = t; ta.geom = geom; ta.tot = S.tot.as<unsigned>(); ta.boff = S.boff.as<unsigned>(); ta.nocc = ra.nocc; ta.lrc = ra.lrc;
+        for (size_t i = 0; i < 3 * nr; ++i) ta.cen.c[i] = centres[i];
+        ta.okey = S.okey.as<unsigned>(); ta.odmax = S.odmax.as<float>(); ta.ocum = S.ocum.as<unsigned>(); ta.work = S.work.as<FeItem>(); ta.counters = counters;
+        ta.info = S.tinfo.as<FeTileInfo>(); ta.num_points = (int)std::min<size_t>(num_points, 0x3fffffff);
+        static const int k1_mult = [] { const char* e = getenv("SSDR_FE_TILE_K1"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 64 ? v : 6; }();
+        // stage 1's size in tile sizes (development; measured on one box, step of 16 rooms: 2, not widened, i.e. a probe for rho alone: 3.053-3.065 ms; 6: 2.962-2.971;
+        // 7 the same as 6; two calls 3.149-3.176): a stage costs the latency of a bucket's reduction (~100 us) however few buckets it holds, so the
+        // first stage should usually be the last
+        ta.k1_mult = k1_mult; ta.k1_widen = k1_mult != 2;
+        const long cap = std::max<long>((long)ctx().num_cu * 16, (long)t.n_total / 64);
+        const int g = (int)std::min<long>((long)ctx().num_cu * 128, cap);
+        ra.items = S.work.as<FeItem>();
+        for (int stage = 1; stage <= 3; ++stage) {
+            if (stage == 1) hipLaunchKernelGGL(fe_tile_order, dim3(R), dim3(FE_NT), 0, s, ta);
+            else if (stage == 2) hipLaunchKernelGGL((fe_tile_plan<2>), dim3(R), dim3(FE_NT), 0, s, ta);
+            else hipLaunchKernelGGL((fe_tile_plan<3>), dim3(R), dim3(FE_NT), 0, s, ta);
+            ra.counters = fe_stage_counters(counters, stage);
+            const int gs = stage < 3 ? g : std::max(1, g / 8);          // stage 3 is the exception: its workgroups take several items each
+            if (fdim == 3 && ldim == 1) hipLaunchKernelGGL((fe_reduce<3, 1, false>), dim3(gs), dim3(FE_RNT), (size_t)fe_pad, s, ra);
+            else hipLaunchKernelGGL((fe_reduce<-1, -1, false>), dim3(gs), dim3(FE_RNT), (size_t)fe_pad, s, ra);
+        }
+        S.tile_clouds = (int)nr;
+    } else if (!fe_image) {
         // The items (buckets) differ in size and are dealt to the workgroups round robin: with twice the resident workgroups (16 per CU: rounds 4-5) the
         // kernel ended with its unluckiest workgroup; with ~ one workgroup per item the hardware's dispatcher does the balancing.  Same box, workgroups
         // per CU (SSDR_FE_WGS): 16: 0.43 ms, 32: 0.39, 64: 0.35, **128: 0.338**, 256: 0.337, 512: 0.343, 4096: slower than 16 (front end 1.08 -> 1.00 ms,
@@ -804,6 +1054,24 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
         SSDR_HIP(hipMemset(reinterpret_cast<unsigned long long*>(counters) + 8, 0, sizeof(h)));
     }
 #endif
+    return SSDR_OK;
+}
+
+void frontend_tile_forget(hipStream_t s) { per_stream<FeState>(s).tile_clouds = 0; }
+
+// what the staged reduction of the last call on `s` did, per room (waits for the stream): the stage it ended in (0 = reduced whole without an order: more than
+// FE_TO_NMAX non-empty buckets, or a grid the partition refuses; -1 = the call was not staged), the buckets it reduced and the room's non-empty buckets
+int frontend_tile_stats(hipStream_t s, int32_t* stage, int32_t* reduced, int32_t* buckets, size_t nr) {
+    FeState& S = per_stream<FeState>(s);
+    SSDR_HIP(hipStreamSynchronize(s));
+    std::vector<FeTileInfo> h(nr);
+    const bool staged = S.tile_clouds > 0 && (size_t)S.tile_clouds == nr;
+    if (staged) SSDR_HIP(hipMemcpy(h.data(), S.tinfo.p, sizeof(FeTileInfo) * nr, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < nr; ++r) {
+        if (stage) stage[r] = staged ? h[r].stage : -1;
+        if (reduced) reduced[r] = staged ? h[r].reduced : -1;
+        if (buckets) buckets[r] = staged ? h[r].n : -1;
+    }
     return SSDR_OK;
 }
 

@@ -541,16 +541,21 @@ int prune_device(const float* d_p, size_t n, float w, const uint8_t* d_rgb, cons
 // frontend.hip: bucket partition + per-bucket LDS reduction (rows of at most 7 words, grids of at most 16384 buckets of 1024 voxels)
 bool frontend_fits(size_t fdim, size_t ldim);
 int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const int32_t* d_c, size_t ldim, const int64_t* room_off, size_t nr, float dl,
-                          float* d_op, float* d_of, int32_t* d_oc, int64_t* d_om, GsParams* prm, hipStream_t s);
+                          float* d_op, float* d_of, int32_t* d_oc, int64_t* d_om, GsParams* prm, hipStream_t s, const float* centres, size_t num_points);
+int frontend_tile_stats(hipStream_t s, int32_t* stage, int32_t* reduced, int32_t* buckets, size_t nr);
+void frontend_tile_forget(hipStream_t s);
 
+// centres (host [nr, 3]) / num_points: the partition path may leave out the buckets that cannot hold one of the num_points rows nearest to a room's centre
+// (ssdr_tile_from_rooms_batch_dev); NULL: every row of every cloud
 int grid_subsample_batch_device(const float* d_p, const float* d_f, size_t fdim, const int32_t* d_c, size_t ldim, const int64_t* room_off, size_t nr, float dl,
-                                float* d_op, float* d_of, int32_t* d_oc, int64_t* d_om, hipStream_t s, int method) {
+                                float* d_op, float* d_of, int32_t* d_oc, int64_t* d_om, hipStream_t s, int method, const float* centres = nullptr, size_t num_points = 0) {
     GsState& S = gs(s);
     if (method != SSDR_SUBSAMPLE_SORT && frontend_fits(fdim, ldim)) {
         S.last_clouds = (int)nr;
         SSDR_TRY(S.params.reserve(sizeof(GsParams) * nr));
-        return frontend_batch_device(d_p, d_f, fdim, d_c, ldim, room_off, nr, dl, d_op, d_of, d_oc, d_om, S.params.as<GsParams>(), s);
+        return frontend_batch_device(d_p, d_f, fdim, d_c, ldim, room_off, nr, dl, d_op, d_of, d_oc, d_om, S.params.as<GsParams>(), s, centres, num_points);
     }
+    if (centres) frontend_tile_forget(s);          // (not staged: the stats of an earlier call on this stream no longer apply)
     CloudTab t; t.nr = (int)nr;
     int toff = 0, maxn = 0; std::vector<int> n_host(nr);
     for (size_t r = 0; r < nr; ++r) {
@@ -635,6 +640,37 @@ int ssdr_grid_subsample_batch_dev(const float* d_points, const float* d_features
     SSDR_TRY(ensure_init());
     return grid_subsample_batch_device(d_points, d_features, d_features ? fdim : 0, d_classes, d_classes ? ldim : 0, cloud_offsets, num_clouds, sampleDl,
                                        d_out_points, d_out_features, d_out_classes, d_out_m, pick_stream(stream), g_batch_method.load());
+}
+
+/* Grid subsample and tile in one call: ssdr_grid_subsample_batch_dev followed by ssdr_tile_select_batch_dev over its rows (d_colors = the sub-sampled
+ * features, d_labels = the sub-sampled classes), with the same tiles bit for bit — but d_sub_* receive only the rows of the spatial buckets that can hold one
+ * of the num_points rows nearest to a cloud's centre (ascending voxel key), d_sub_m their count, and d_out_idx counts among those rows.  Stateless: which
+ * buckets are reduced follows from this call's inputs alone.  Under SSDR_SUBSAMPLE_SORT (or rows of more than 7 words) every row is produced. */
+int ssdr_tile_from_rooms_batch_dev(const float* d_points, const float* d_features, size_t fdim, const int32_t* d_classes, size_t ldim,
+                                   const int64_t* cloud_offsets, size_t num_clouds, float sampleDl,
+                                   float* d_sub_points, float* d_sub_features, int32_t* d_sub_classes, int64_t* d_sub_m,
+                                   const float* centers, size_t num_points, const int32_t* d_perm, const float* d_dup_u, float color_scale,
+                                   float* d_out_xyz, float* d_out_feat, int32_t* d_out_idx, int32_t* d_out_labels, void* stream) {
+    if (!d_points || !d_sub_points || !cloud_offsets || !d_sub_m || num_clouds == 0 || num_clouds > RADIX_MAX_SEG) { set_error("tile_from_rooms_batch: bad arguments (1..%d clouds)", RADIX_MAX_SEG); return SSDR_ERR_INVALID; }
+    if (!(sampleDl > 0.f)) { set_error("tile_from_rooms_batch: sampleDl must be > 0"); return SSDR_ERR_INVALID; }
+    if (d_features && (!fdim || !d_sub_features)) { set_error("tile_from_rooms_batch: features given without fdim / output"); return SSDR_ERR_INVALID; }
+    if (d_classes && (!ldim || !d_sub_classes)) { set_error("tile_from_rooms_batch: classes given without ldim / output"); return SSDR_ERR_INVALID; }
+    if (!centers || !d_perm || !d_dup_u || !d_out_xyz || num_points == 0) { set_error("tile_from_rooms_batch: bad tile arguments"); return SSDR_ERR_INVALID; }
+    if (d_out_labels && (!d_classes || ldim != 1)) { set_error("tile_from_rooms_batch: tile labels need one class column"); return SSDR_ERR_INVALID; }
+    SSDR_TRY(ensure_init());
+    SSDR_TRY(grid_subsample_batch_device(d_points, d_features, d_features ? fdim : 0, d_classes, d_classes ? ldim : 0, cloud_offsets, num_clouds, sampleDl,
+                                         d_sub_points, d_sub_features, d_sub_classes, d_sub_m, pick_stream(stream), g_batch_method.load(), centers, num_points));
+    return ssdr_tile_select_batch_dev(d_sub_points, d_features ? d_sub_features : nullptr, d_features ? (int)fdim : 0, d_sub_m, cloud_offsets, num_clouds, centers, num_points,
+                                      d_perm, d_dup_u, color_scale, d_out_xyz, d_out_feat, d_out_idx, d_out_labels ? d_sub_classes : nullptr, d_out_labels, stream);
+}
+
+/* What the last ssdr_tile_from_rooms_batch_dev on `stream` reduced (waits for it), per cloud (int32 [num_clouds] each, may be NULL): the stage its reduction
+ * ended in (1: the first stage's buckets sufficed or were the whole cloud, 2: the estimate sufficed, 3: the rest of the cloud was needed; 0: reduced whole without an order; -1:
+ * the call took the sort), the buckets reduced and the cloud's non-empty buckets. */
+int ssdr_tile_from_rooms_stats(void* stream, int32_t* out_stage, int32_t* out_reduced, int32_t* out_buckets, size_t num_clouds) {
+    if (num_clouds == 0 || num_clouds > RADIX_MAX_SEG) { set_error("tile_from_rooms_stats: bad arguments"); return SSDR_ERR_INVALID; }
+    SSDR_TRY(ensure_init());
+    return frontend_tile_stats(pick_stream(stream), out_stage, out_reduced, out_buckets, num_clouds);
 }
 
 /* which implementation ssdr_grid_subsample_batch_dev uses: SSDR_SUBSAMPLE_AUTO (default: the bucket partition of frontend.hip for rows of at most 7 words,

@@ -382,6 +382,13 @@ class HotPath:
         cfg, L = self.cfg, _lib.lib()
         st = self.front_stream
         _lib.check(L.ssdr_grid_subsample_set_method(self.subsample_method))
+        # the bucket partition reduces only the buckets the tiles' rows can lie in (sub_* / sub_m then hold those rows); SSDR_FE_TILE_PRUNE=0 (development:
+        # A/B runs) and the sort keep the two calls
+        if self.subsample_method == 0 and os.environ.get("SSDR_FE_TILE_PRUNE", "1") != "0":
+            _lib.check(L.ssdr_tile_from_rooms_batch_dev(self.raw_p.ptr, self.raw_c.ptr, 3, self.raw_l.ptr, 1, _lib.ptr(self.room_off), self.B, cfg.sub_grid_size,
+                                                        self.sub_p.ptr, self.sub_c.ptr, self.sub_l.ptr, self.sub_m.ptr, _lib.ptr(self.centers), cfg.num_points,
+                                                        self.perm.ptr, self.dup.ptr, 1.0 / 255.0, self.xyz.ptr, self.feat.ptr, None, self.tile_l.ptr, st))
+            return
         _lib.check(L.ssdr_grid_subsample_batch_dev(self.raw_p.ptr, self.raw_c.ptr, 3, self.raw_l.ptr, 1, _lib.ptr(self.room_off), self.B, cfg.sub_grid_size,
                                                    self.sub_p.ptr, self.sub_c.ptr, self.sub_l.ptr, self.sub_m.ptr, st))
         _lib.check(L.ssdr_tile_select_batch_dev(self.sub_p.ptr, self.sub_c.ptr, 3, self.sub_m.ptr, _lib.ptr(self.room_off), self.B, _lib.ptr(self.centers),
