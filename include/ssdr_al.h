@@ -206,6 +206,11 @@ int ssdr_tile_from_rooms_batch_dev(const float* d_points, const float* d_feature
  * (1: the first stage's buckets sufficed or were the whole cloud, 2: the set estimated from the first stage's points per voxel sufficed, 3: the rest of the
  * cloud was needed, 0: reduced whole without an order, -1: the sort), the buckets reduced, the cloud's non-empty buckets. */
 int ssdr_tile_from_rooms_stats(void* stream, int32_t* out_stage, int32_t* out_reduced, int32_t* out_buckets, size_t num_clouds);
+/* Per cloud of the last ssdr_tile_from_rooms_batch_dev on `stream` (waits for it; int64 [num_clouds] each, may be NULL): the 32-byte records its partition wrote
+ * and the cloud's points.  The partition writes only the records of the buckets a stage reduces: records < points for a cloud whose first stage sufficed with a
+ * part of its buckets, records == points for a cloud that went on to a later stage or was reduced whole.  -1 / -1 when the call took the sort; records -1 under
+ * SSDR_FE_SCATTER_PRUNE=0 (development: the one scatter of every record, which does not count). */
+int ssdr_tile_from_rooms_scatter_stats(void* stream, int64_t* out_scattered, int64_t* out_points, size_t num_clouds);
 /* Test-time variant (S3/s3dis_dataset_test.py:105-143): the same tile, plus the possibility-map update
  * possibility[idx] += (1 - dists/max(dists))^2 over the tile's (un-padded) points (float64 map, float32 dists) and,
  * optionally, min / argmin of the updated map (the next pick: :106-108).  An empty cloud (*d_m <= 0): the tile outputs and the

@@ -23,7 +23,9 @@
 //   move              every bucket's rows to their final position
 //
 // HBM traffic: 12 N (minmax) + 12 N (count) + 28 N + 32 N (scatter) + 32 N + 32 M (reduce) + 32 M + 28 M (move) bytes for N points and M
-// voxels, against 28 (N + M) algorithmic.  Clouds whose grid does not fit (more than FE_NBMAX buckets of 1024 voxels) or that
+// voxels, against 28 (N + M) algorithmic.  The staged reduction of ssdr_tile_from_rooms_batch_dev (below) orders a room's buckets BEFORE the scatter and writes and
+// reduces only the share p of the points that lies in stage 1's buckets: 12 N + 12 N + 28 N + 32 p N (scatter) + 32 p N + 32 p M (reduce) + (32 + 28) p M (move);
+// p = 0.42 on the bench's rooms.  A room that goes on to stage 2 pays 28 N more (a second read of its points) for the other 32 (1 - p) N of records.  Clouds whose grid does not fit (more than FE_NBMAX buckets of 1024 voxels) or that
 // hold a voxel of more than FE_CAP points are flagged (ssdr_grid_subsample_status) and belong to the sort-based entry point.
 #include "ssdr_internal.hpp"
 #include "block_prims.hpp"
@@ -68,6 +70,9 @@ struct FeGeom {
 struct FeItem { unsigned base, n, rb, sx; float org[3]; float dl; };       // base: first record (absolute); rb = cloud << 16 | bucket
 
 struct FeTab { int nr; int chunks_max; int ovf_cap; int n_total; int off[RADIX_MAX_SEG + 1]; };
+struct FeTileInfo { int n, k1, k2, stage, reduced, pad0, pad1, pad2; };      // staged reduction, per room; stage: 0 = reduced whole without an order, 1..3 = the stage that was the last
+// per-room count of the records the pruned scatter wrote (64-bit words behind the 64 int counters; zeroed by fe_params)
+__host__ __device__ __forceinline__ unsigned long long* fe_scatter_counters(int* counters) { return reinterpret_cast<unsigned long long*>(counters + 64); }
 
 // voxel coordinates of a point (grid_subsampling.cpp:53-56: floor((p - origin) / dl), the same fp32 operations); false when the point
 // falls outside the grid the bounding box gives (a wrapped size_t in the reference: only NaNs and overflowing coordinates get here)
@@ -104,6 +109,7 @@ __global__ __launch_bounds__(BS) void fe_params(FeTab t, const float* partial, f
     block_minmax3(mn, mx, s_mm);
     if (threadIdx.x == 0) {
         if (r == 0) { for (int i = 0; i < 64; ++i) counters[i] = 0; }         // [0] work items, [3] overflow rows; [32..56) the same per stage of the staged reduction
+        fe_scatter_counters(counters)[r] = 0ull;
         GsParams p; FeGeom g;
         const float inv = 1 / dl;               // grid_subsampling.cpp:27-31
         float nd[3];
@@ -237,16 +243,52 @@ __device__ __forceinline__ FePoint fe_load_point(const float* __restrict__ Pr, c
     }
     return pt;
 }
-template <int FD, int LD>
+constexpr unsigned FE_NOSLOT = 0xffffffffu;      // no record for this point; as a cursor: a bucket this pass does not write (offsets stay <= 0x3fffffff)
+// one record to its slot
+__device__ __forceinline__ void fe_store_record(uint4* R, const FePoint& pt, int i, unsigned slot, int tid) {
+    // (non-temporal stores here: 2.6x slower — the L2 merges the two halves of a record, and little else: a chunk adds ~4 records to a bucket)
+#if FE_PAIR_STORES
+    // the two 16-byte halves of a record leave from ADJACENT lanes, so a store instruction carries 32 runs of 32 bytes instead of 64 of 16: lanes
+    // 2j and 2j + 1 swap a half each (the even lane hands over its second half and takes the odd lane's first)
+    const bool odd = tid & 1;
+    const uint32_t a0 = __float_as_uint(pt.x), a1 = __float_as_uint(pt.y), a2 = __float_as_uint(pt.z), a3 = (uint32_t)i;
+    const uint32_t b0 = pt.w[0], b1 = pt.w[1], b2 = pt.w[2], b3 = pt.w[3];
+    const uint32_t g0 = fe_swap1(odd ? a0 : b0), g1 = fe_swap1(odd ? a1 : b1), g2 = fe_swap1(odd ? a2 : b2), g3 = fe_swap1(odd ? a3 : b3);
+    const unsigned pslot = fe_swap1(slot);
+    const unsigned se = odd ? pslot : slot, so = odd ? slot : pslot;          // the even lane's record, the odd lane's record
+    if (se != FE_NOSLOT) R[2 * (size_t)se + (odd ? 1 : 0)] = odd ? make_uint4(g0, g1, g2, g3) : make_uint4(a0, a1, a2, a3);
+    if (so != FE_NOSLOT) R[2 * (size_t)so + (odd ? 1 : 0)] = odd ? make_uint4(b0, b1, b2, b3) : make_uint4(g0, g1, g2, g3);
+#else
+    if (slot != FE_NOSLOT) {
+        R[2 * (size_t)slot] = make_uint4(__float_as_uint(pt.x), __float_as_uint(pt.y), __float_as_uint(pt.z), (uint32_t)i);
+        R[2 * (size_t)slot + 1] = make_uint4(pt.w[0], pt.w[1], pt.w[2], pt.w[3]);
+    }
+#endif
+}
+// MODE 0: every bucket (ssdr_grid_subsample_batch_dev, and the staged reduction under SSDR_FE_SCATTER_PRUNE=0).  The staged reduction knows stage 1's buckets before
+// a record is written (fe_tile_order runs first and leaves one flag per bucket), so MODE 1 writes the records of the flagged buckets only: the cursor of every
+// other bucket is FE_NOSLOT from the start, and a point that finds it gets no slot and no store (a lane pair with one such point stores one record's two halves).  The layout
+// (boff, cntm) is that of MODE 0: an unflagged bucket's range is simply not written, and nobody reads it — unless its room goes on to stage 2: MODE 2, launched behind
+// fe_tile_plan<2>, then writes exactly the points of the UNflagged buckets of such rooms (a second read of the room's points) and leaves at once for every other room.
+// Both count the records they wrote per room (one atomic per workgroup: ssdr_tile_from_rooms_scatter_stats).  All twelve points' loads still leave together, features
+// and labels of skipped points included: loading those only for points with a slot (a second round of loads behind the cursors) read 0.018 ms per step slower in
+// every one of five interleaved runs (profiles/r09_frontend_scatter_prune.md): the rooms' rows are shuffled, so hardly a 32-byte sector is spared.
+template <int FD, int LD, int MODE>
 __global__ __launch_bounds__(FE_SNT) void fe_scatter(FeTab t, const float* __restrict__ P, const float* __restrict__ F, int fdim, const int* __restrict__ cls, int ldim,
-                                                    const FeGeom* __restrict__ geom, const unsigned* __restrict__ cntm, const unsigned* __restrict__ boff, uint4* rec) {
+                                                    const FeGeom* __restrict__ geom, const unsigned* __restrict__ cntm, const unsigned* __restrict__ boff, uint4* rec,
+                                                    const unsigned char* __restrict__ flag, const FeTileInfo* __restrict__ info, unsigned long long* nscat) {
     __shared__ unsigned s_cur[FE_NBMAX];
     const int r = blockIdx.y, c = blockIdx.x, tid = threadIdx.x;
     const FeGeom g = geom[r];
     if (!g.ok || c * FE_CH >= g.n) return;
+    if (MODE == 2 && info[r].stage < 2) return;          // stage 1 sufficed (or took the room whole)
     const unsigned* row = cntm + ((size_t)r * t.chunks_max + c) * FE_NBMAX;
     const unsigned* bo = boff + (size_t)r * (FE_NBMAX + 1);
-    for (int b = tid; b < g.nb; b += FE_SNT) s_cur[b] = bo[b] + row[b];
+    if (MODE == 0) { for (int b = tid; b < g.nb; b += FE_SNT) s_cur[b] = bo[b] + row[b]; }
+    else {
+        const unsigned char* fl = flag + (size_t)r * FE_NBMAX;
+        for (int b = tid; b < g.nb; b += FE_SNT) s_cur[b] = (fl[b] != 0) == (MODE == 1) ? bo[b] + row[b] : FE_NOSLOT;
+    }
     __syncthreads();
     const size_t o = (size_t)t.off[r];
     const float* Pr = P + 3 * o;
@@ -254,6 +296,7 @@ __global__ __launch_bounds__(FE_SNT) void fe_scatter(FeTab t, const float* __res
     const int* Cr = cls ? cls + o * ldim : nullptr;
     uint4* R = rec + 2 * o;
     const int lo = c * FE_CH, hi = min(g.n, (c + 1) * FE_CH);
+    unsigned kept = 0;
     for (int i0 = lo; i0 < hi; i0 += FE_SNT * FE_PPT) {
         FePoint cur[FE_PPT];
 #pragma unroll
@@ -262,26 +305,25 @@ __global__ __launch_bounds__(FE_SNT) void fe_scatter(FeTab t, const float* __res
         for (int k = 0; k < FE_PPT; ++k) {
             const int i = i0 + k * FE_SNT + tid;
             int ix, iy, iz;
-            unsigned slot = 0xffffffffu;
-            if (i < hi && fe_voxel(g, cur[k].x, cur[k].y, cur[k].z, ix, iy, iz)) slot = atomicAdd(&s_cur[fe_bucket(g, ix, iy, iz)], 1u);
-            // (non-temporal stores here: 2.6x slower — the L2 merges the two halves of a record, and little else: a chunk adds ~4 records to a bucket)
-#if FE_PAIR_STORES
-            // the two 16-byte halves of a record leave from ADJACENT lanes, so a store instruction carries 32 runs of 32 bytes instead of 64 of 16: lanes
-            // 2j and 2j + 1 swap a half each (the even lane hands over its second half and takes the odd lane's first)
-            const bool odd = tid & 1;
-            const uint32_t a0 = __float_as_uint(cur[k].x), a1 = __float_as_uint(cur[k].y), a2 = __float_as_uint(cur[k].z), a3 = (uint32_t)i;
-            const uint32_t b0 = cur[k].w[0], b1 = cur[k].w[1], b2 = cur[k].w[2], b3 = cur[k].w[3];
-            const uint32_t g0 = fe_swap1(odd ? a0 : b0), g1 = fe_swap1(odd ? a1 : b1), g2 = fe_swap1(odd ? a2 : b2), g3 = fe_swap1(odd ? a3 : b3);
-            const unsigned pslot = fe_swap1(slot);
-            const unsigned se = odd ? pslot : slot, so = odd ? slot : pslot;          // the even lane's record, the odd lane's record
-            if (se != 0xffffffffu) R[2 * (size_t)se + (odd ? 1 : 0)] = odd ? make_uint4(g0, g1, g2, g3) : make_uint4(a0, a1, a2, a3);
-            if (so != 0xffffffffu) R[2 * (size_t)so + (odd ? 1 : 0)] = odd ? make_uint4(b0, b1, b2, b3) : make_uint4(g0, g1, g2, g3);
-#else
-            if (slot != 0xffffffffu) {
-                R[2 * (size_t)slot] = make_uint4(__float_as_uint(cur[k].x), __float_as_uint(cur[k].y), __float_as_uint(cur[k].z), (uint32_t)i);
-                R[2 * (size_t)slot + 1] = make_uint4(cur[k].w[0], cur[k].w[1], cur[k].w[2], cur[k].w[3]);
+            unsigned slot = FE_NOSLOT;
+            if (i < hi && fe_voxel(g, cur[k].x, cur[k].y, cur[k].z, ix, iy, iz)) {
+                unsigned* cp = &s_cur[fe_bucket(g, ix, iy, iz)];
+                if (MODE == 0 || *cp != FE_NOSLOT) slot = atomicAdd(cp, 1u);
             }
-#endif
+            if (MODE != 0) kept += slot != FE_NOSLOT ? 1u : 0u;
+            fe_store_record(R, cur[k], i, slot, tid);
+        }
+    }
+    if (MODE != 0) {          // the workgroup's records: the cursors are done with, their first words carry the waves' sums
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) kept += __shfl_xor(kept, m);
+        __syncthreads();
+        if ((tid & 63) == 0) s_cur[tid >> 6] = kept;
+        __syncthreads();
+        if (tid == 0) {
+            unsigned long long sum = 0;
+            for (int w = 0; w < FE_SNT / 64; ++w) sum += s_cur[w];
+            if (sum) atomicAdd(&nscat[r], sum);
         }
     }
 }
@@ -724,9 +766,8 @@ constexpr int FE_TO_NMAX = 8192;     // non-empty buckets of a room the order is
 constexpr int FE_TO_KBITS = 14;      // low bits of a sort word: the bucket (FE_NBMAX = 2^14); above them 18 bits of the least distance's pattern
 static_assert(FE_NBMAX == 1 << FE_TO_KBITS, "bucket bits of the order's sort words");
 struct FeCentres { float c[3 * RADIX_MAX_SEG]; };
-struct FeTileInfo { int n, k1, k2, stage, reduced, pad0, pad1, pad2; };      // stage: 0 = reduced whole without an order, 1..3 = the stage that was the last
 struct FeTileArgs {
-    FeTab t; FeCentres cen; const FeGeom* geom; const unsigned* tot; const unsigned* boff; unsigned* nocc; unsigned char* lrc;
+    FeTab t; FeCentres cen; const FeGeom* geom; const unsigned* tot; const unsigned* boff; unsigned* nocc; unsigned char* lrc; unsigned char* flag;
     unsigned* okey; float* odmax; unsigned* ocum; FeItem* work; int* counters; FeTileInfo* info; int num_points, k1_mult, k1_widen;
 };
 // per stage s = 1..3 a block of 8 counters behind the whole-room ones: [0] items of the stage's work list, [3] the overflow rows' cursor
@@ -769,7 +810,8 @@ __device__ __forceinline__ FeItem fe_tile_item(const FeTileArgs& a, const FeGeom
 
 // One workgroup per room, after fe_bscan: every non-empty bucket reads as empty to the row kernels until a stage reduces it; the room's buckets by
 // ascending least distance (sort word = 18 bits of the distance's pattern, rounded DOWN: still a lower bound | bucket: no two words are equal, the
-// order is the inputs'), their greatest distances and running point counts in that order; stage 1's work items.
+// order is the inputs'), their greatest distances and running point counts in that order; stage 1's work items.  It needs geom, tot, boff and the centres, no
+// record: it runs in front of the scatter and leaves it one flag per non-empty bucket, "stage 1 reduces this bucket" (every bucket of a room without an order).
 __global__ __launch_bounds__(FE_NT) void fe_tile_order(FeTileArgs a) {
     __shared__ unsigned s_k[FE_TO_NMAX];
     __shared__ unsigned s_m;
@@ -803,7 +845,10 @@ __global__ __launch_bounds__(FE_NT) void fe_tile_order(FeTileArgs a) {
     if (n > FE_TO_NMAX) {          // no order: the whole room in stage 1
         if (tid == 0) { s_base = atomicAdd(&cb[0], n); s_n = 0; }
         __syncthreads();
-        for (int b = tid; b < g.nb; b += FE_NT) if (tot[b]) a.work[(size_t)s_base + atomicAdd(&s_n, 1)] = fe_tile_item(a, g, r, b);
+        for (int b = tid; b < g.nb; b += FE_NT) if (tot[b]) {
+            a.work[(size_t)s_base + atomicAdd(&s_n, 1)] = fe_tile_item(a, g, r, b);
+            if (a.flag) a.flag[(size_t)r * FE_NBMAX + b] = 1;
+        }
         if (tid == 0) a.info[r] = ti;
         return;
     }
@@ -859,6 +904,8 @@ __global__ __launch_bounds__(FE_NT) void fe_tile_order(FeTileArgs a) {
     if (tid == 0) s_base = k1 ? atomicAdd(&cb[0], k1) : 0;
     __syncthreads();
     for (int i = tid; i < k1; i += FE_NT) a.work[(size_t)s_base + i] = fe_tile_item(a, g, r, (int)(s_k[i] & (FE_NBMAX - 1)));
+    // what the pruned scatter goes by: every non-empty bucket's flag, written anew by every call (an empty bucket's is never looked at: no point finds its cursor)
+    if (a.flag) for (int i = tid; i < n; i += FE_NT) a.flag[(size_t)r * FE_NBMAX + (s_k[i] & (FE_NBMAX - 1))] = i < k1 ? 1 : 0;
     ti.k1 = k1; ti.k2 = k1; ti.reduced = k1; ti.stage = 1;
     if (tid == 0) a.info[r] = ti;
 }
@@ -927,6 +974,7 @@ __global__ __launch_bounds__(FE_NT) void fe_tile_plan(FeTileArgs a) {
 struct FeState {
     DevBuf partial, geom, cntm, tot, boff, items, counters, rec, nocc, trow, lrc, pre, rowcnt, rcp; bool rcp_ready = false;
     DevBuf okey, odmax, ocum, work, tinfo; int tile_clouds = 0;          // the staged reduction's tables; rooms of the last call if it was staged
+    DevBuf flag; bool pruned = false; std::vector<long long> room_n;      // [room][FE_NBMAX] bytes: stage 1 reduces this bucket; the last staged call: pruned scatter? its rooms' points
 };
 
 }  // namespace
@@ -959,7 +1007,7 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
     static const int fe_pad = [] { const char* e = getenv("SSDR_FE_PADLDS"); return e ? atoi(e) : 0; }();      // (development: unused dynamic LDS caps the workgroups per CU)
     t.ovf_cap = fe_image ? std::max(65536, t.n_total / 8) : t.n_total;
     const unsigned R = (unsigned)nr;
-    SSDR_TRY(S.partial.reserve(24 * (size_t)PB * nr)); SSDR_TRY(S.geom.reserve(sizeof(FeGeom) * nr)); SSDR_TRY(S.counters.reserve(256));
+    SSDR_TRY(S.partial.reserve(24 * (size_t)PB * nr)); SSDR_TRY(S.geom.reserve(sizeof(FeGeom) * nr)); SSDR_TRY(S.counters.reserve(256 + 8 * RADIX_MAX_SEG));
     SSDR_TRY(S.cntm.reserve(4 * (size_t)FE_NBMAX * t.chunks_max * nr)); SSDR_TRY(S.tot.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.boff.reserve(4 * (size_t)(FE_NBMAX + 1) * nr));
     SSDR_TRY(S.items.reserve(sizeof(FeItem) * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.nocc.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.trow.reserve(4 * (size_t)FE_NBMAX * nr));
     SSDR_TRY(S.lrc.reserve((size_t)FE_NBMAX * FE_LR * nr)); SSDR_TRY(S.pre.reserve(2 * (size_t)FE_NBMAX * FE_LR * nr));
@@ -971,6 +1019,31 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
         S.rcp_ready = true;
     }
     FeGeom* geom = S.geom.as<FeGeom>(); int* counters = S.counters.as<int>(); FeItem* items = S.items.as<FeItem>();
+    FeRedArgs ra; ra.t = t; ra.items = items; ra.prm = prm; ra.counters = counters; ra.rcp = S.rcp.as<float>(); ra.rec = S.rec.as<uint4>();
+    ra.nocc = S.nocc.as<unsigned>(); ra.trow = S.trow.as<unsigned>(); ra.lrc = S.lrc.as<unsigned char>(); ra.fdim = (int)fdim; ra.ldim = (int)ldim;
+    // the staged reduction (centres given).  Stage 1's buckets follow from the buckets' point counts, their boxes and the centres: all there after fe_bscan, so the
+    // order comes first and the scatter writes the records of those buckets only.  SSDR_FE_SCATTER_PRUNE=0 (development: A/B runs in one build) keeps the one
+    // scatter of every record, with the order behind it.
+    const bool staged = centres && !fe_image;
+    static const bool fe_scatter_prune = [] { const char* e = getenv("SSDR_FE_SCATTER_PRUNE"); return !(e && e[0] == '0'); }();
+    const bool prune = staged && fe_scatter_prune;
+    FeTileArgs ta;
+    if (staged) {
+        SSDR_TRY(S.okey.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.odmax.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.ocum.reserve(4 * (size_t)FE_NBMAX * nr));
+        SSDR_TRY(S.work.reserve(sizeof(FeItem) * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.tinfo.reserve(sizeof(FeTileInfo) * RADIX_MAX_SEG));
+        if (prune) SSDR_TRY(S.flag.reserve((size_t)FE_NBMAX * nr));
+        ta.t = t; ta.geom = geom; ta.tot = S.tot.as<unsigned>(); ta.boff = S.boff.as<unsigned>(); ta.nocc = ra.nocc; ta.lrc = ra.lrc;
+        ta.flag = prune ? S.flag.as<unsigned char>() : nullptr;
+        for (size_t i = 0; i < 3 * nr; ++i) ta.cen.c[i] = centres[i];
+        ta.okey = S.okey.as<unsigned>(); ta.odmax = S.odmax.as<float>(); ta.ocum = S.ocum.as<unsigned>(); ta.work = S.work.as<FeItem>(); ta.counters = counters;
+        ta.info = S.tinfo.as<FeTileInfo>(); ta.num_points = (int)std::min<size_t>(num_points, 0x3fffffff);
+        static const int k1_mult = [] { const char* e = getenv("SSDR_FE_TILE_K1"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 64 ? v : 6; }();
+        // stage 1's size in tile sizes (development; measured on one box, step of 16 rooms: 2, not widened, i.e. a probe for rho alone: 3.053-3.065 ms; 6: 2.962-2.971;
+        // 7 the same as 6; two calls 3.149-3.176): a stage costs the latency of a bucket's reduction (~100 us) however few buckets it holds, so the
+        // first stage should usually be the last.  With the pruned scatter a smaller stage 1 also saves scattered writes, and a miss costs a second read of the room.
+        ta.k1_mult = k1_mult; ta.k1_widen = k1_mult != 2;
+    }
+    const unsigned char* flag = S.flag.as<unsigned char>(); const FeTileInfo* tinfo = S.tinfo.as<FeTileInfo>(); unsigned long long* nscat = fe_scatter_counters(counters);
     // profiler sites (ssdr_prof_enable; bench.py's roofline leg): `work` = the algorithmic bytes a site is charged with — the one read of the inputs
     // (28 B per point) goes to the scatter, the one write of the rows (28 B per voxel: the count is the device's, bench.py adds it) to the reduction
     {
@@ -980,46 +1053,45 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
     hipLaunchKernelGGL(fe_count, dim3(t.chunks_max, R), dim3(FE_NT), 0, s, t, d_p, geom, prm, S.cntm.as<unsigned>());
     hipLaunchKernelGGL(fe_colscan, dim3(FE_NBMAX / BS, R), dim3(BS), 0, s, t, geom, S.cntm.as<unsigned>(), S.tot.as<unsigned>());
     hipLaunchKernelGGL(fe_bscan, dim3(R), dim3(FE_NT), 0, s, t, geom, S.tot.as<unsigned>(), S.boff.as<unsigned>(), items, counters);
+    if (prune) hipLaunchKernelGGL(fe_tile_order, dim3(R), dim3(FE_NT), 0, s, ta);
     }
+#define FE_LAUNCH_SCATTER(MODE)                                                                                                                                              \
+    do {                                                                                                                                                                     \
+        if (fdim == 3 && ldim == 1)                                                                                                                                          \
+            hipLaunchKernelGGL((fe_scatter<3, 1, MODE>), dim3(t.chunks_max, R), dim3(FE_SNT), 0, s, t, d_p, d_f, (int)fdim, (const int*)d_c, (int)ldim, geom, S.cntm.as<unsigned>(), \
+                               S.boff.as<unsigned>(), S.rec.as<uint4>(), flag, tinfo, nscat);                                                                                \
+        else                                                                                                                                                                 \
+            hipLaunchKernelGGL((fe_scatter<-1, -1, MODE>), dim3(t.chunks_max, R), dim3(FE_SNT), 0, s, t, d_p, d_f, (int)fdim, (const int*)d_c, (int)ldim, geom, S.cntm.as<unsigned>(), \
+                               S.boff.as<unsigned>(), S.rec.as<uint4>(), flag, tinfo, nscat);                                                                                \
+    } while (0)
     {
     ProfScope prof("fe_scatter", s, (double)(12 + 4 * (fdim + ldim)) * (double)t.n_total);
-    if (fdim == 3 && ldim == 1)
-        hipLaunchKernelGGL((fe_scatter<3, 1>), dim3(t.chunks_max, R), dim3(FE_SNT), 0, s, t, d_p, d_f, (int)fdim, (const int*)d_c, (int)ldim, geom, S.cntm.as<unsigned>(), S.boff.as<unsigned>(),
-                           S.rec.as<uint4>());
-    else
-        hipLaunchKernelGGL((fe_scatter<-1, -1>), dim3(t.chunks_max, R), dim3(FE_SNT), 0, s, t, d_p, d_f, (int)fdim, (const int*)d_c, (int)ldim, geom, S.cntm.as<unsigned>(), S.boff.as<unsigned>(),
-                           S.rec.as<uint4>());
+    if (prune) FE_LAUNCH_SCATTER(1);
+    else FE_LAUNCH_SCATTER(0);
     }
-    FeRedArgs ra; ra.t = t; ra.items = items; ra.prm = prm; ra.counters = counters; ra.rcp = S.rcp.as<float>(); ra.rec = S.rec.as<uint4>();
-    ra.nocc = S.nocc.as<unsigned>(); ra.trow = S.trow.as<unsigned>(); ra.lrc = S.lrc.as<unsigned char>(); ra.fdim = (int)fdim; ra.ldim = (int)ldim;
     {
     ProfScope prof("fe_reduce", s, 0.0);
-    if (centres && !fe_image) {
+    if (staged) {
         // the same kernel per stage, over the stage's work list; the lists' lengths are the device's (workgroups beyond them exit at once)
-        SSDR_TRY(S.okey.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.odmax.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.ocum.reserve(4 * (size_t)FE_NBMAX * nr));
-        SSDR_TRY(S.work.reserve(sizeof(FeItem) * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.tinfo.reserve(sizeof(FeTileInfo) * RADIX_MAX_SEG));
-        FeTileArgs ta; ta.t = t; ta.geom = geom; ta.tot = S.tot.as<unsigned>(); ta.boff = S.boff.as<unsigned>(); ta.nocc = ra.nocc; ta.lrc = ra.lrc;
-        for (size_t i = 0; i < 3 * nr; ++i) ta.cen.c[i] = centres[i];
-        ta.okey = S.okey.as<unsigned>(); ta.odmax = S.odmax.as<float>(); ta.ocum = S.ocum.as<unsigned>(); ta.work = S.work.as<FeItem>(); ta.counters = counters;
-        ta.info = S.tinfo.as<FeTileInfo>(); ta.num_points = (int)std::min<size_t>(num_points, 0x3fffffff);
-        static const int k1_mult = [] { const char* e = getenv("SSDR_FE_TILE_K1"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 64 ? v : 6; }();
-        // stage 1's size in tile sizes (development; measured on one box, step of 16 rooms: 2, not widened, i.e. a probe for rho alone: 3.053-3.065 ms; 6: 2.962-2.971;
-        // 7 the same as 6; two calls 3.149-3.176): a stage costs the latency of a bucket's reduction (~100 us) however few buckets it holds, so the
-        // first stage should usually be the last
-        ta.k1_mult = k1_mult; ta.k1_widen = k1_mult != 2;
         const long cap = std::max<long>((long)ctx().num_cu * 16, (long)t.n_total / 64);
         const int g = (int)std::min<long>((long)ctx().num_cu * 128, cap);
         ra.items = S.work.as<FeItem>();
         for (int stage = 1; stage <= 3; ++stage) {
-            if (stage == 1) hipLaunchKernelGGL(fe_tile_order, dim3(R), dim3(FE_NT), 0, s, ta);
-            else if (stage == 2) hipLaunchKernelGGL((fe_tile_plan<2>), dim3(R), dim3(FE_NT), 0, s, ta);
+            if (stage == 1) { if (!prune) hipLaunchKernelGGL(fe_tile_order, dim3(R), dim3(FE_NT), 0, s, ta); }
+            else if (stage == 2) {
+                hipLaunchKernelGGL((fe_tile_plan<2>), dim3(R), dim3(FE_NT), 0, s, ta);
+                // the records stage 1 did not need, for the rooms that go on (a second read of their points); every other room's workgroups leave at once
+                if (prune) FE_LAUNCH_SCATTER(2);
+            }
             else hipLaunchKernelGGL((fe_tile_plan<3>), dim3(R), dim3(FE_NT), 0, s, ta);
             ra.counters = fe_stage_counters(counters, stage);
             const int gs = stage < 3 ? g : std::max(1, g / 8);          // stage 3 is the exception: its workgroups take several items each
             if (fdim == 3 && ldim == 1) hipLaunchKernelGGL((fe_reduce<3, 1, false>), dim3(gs), dim3(FE_RNT), (size_t)fe_pad, s, ra);
             else hipLaunchKernelGGL((fe_reduce<-1, -1, false>), dim3(gs), dim3(FE_RNT), (size_t)fe_pad, s, ra);
         }
-        S.tile_clouds = (int)nr;
+        S.tile_clouds = (int)nr; S.pruned = prune;
+        S.room_n.assign(nr, 0);
+        for (size_t r = 0; r < nr; ++r) S.room_n[r] = (long long)(room_off[r + 1] - room_off[r]);
     } else if (!fe_image) {
         // The items (buckets) differ in size and are dealt to the workgroups round robin: with twice the resident workgroups (16 per CU: rounds 4-5) the
         // kernel ended with its unluckiest workgroup; with ~ one workgroup per item the hardware's dispatcher does the balancing.  Same box, workgroups
@@ -1071,6 +1143,21 @@ int frontend_tile_stats(hipStream_t s, int32_t* stage, int32_t* reduced, int32_t
         if (stage) stage[r] = staged ? h[r].stage : -1;
         if (reduced) reduced[r] = staged ? h[r].reduced : -1;
         if (buckets) buckets[r] = staged ? h[r].n : -1;
+    }
+    return SSDR_OK;
+}
+
+// what the scatter of the last staged call on `s` wrote, per room (waits for the stream): the records written (stage 1's pass plus the second pass of a room that went
+// on; -1 under SSDR_FE_SCATTER_PRUNE=0, where the one scatter of every record does not count) and the room's points; -1 / -1 when the call was not staged
+int frontend_scatter_stats(hipStream_t s, int64_t* scattered, int64_t* points, size_t nr) {
+    FeState& S = per_stream<FeState>(s);
+    SSDR_HIP(hipStreamSynchronize(s));
+    std::vector<unsigned long long> h(nr);
+    const bool staged = S.tile_clouds > 0 && (size_t)S.tile_clouds == nr;
+    if (staged && S.pruned) SSDR_HIP(hipMemcpy(h.data(), fe_scatter_counters(S.counters.as<int>()), sizeof(unsigned long long) * nr, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < nr; ++r) {
+        if (scattered) scattered[r] = staged && S.pruned ? (int64_t)h[r] : -1;
+        if (points) points[r] = staged ? (int64_t)S.room_n[r] : -1;
     }
     return SSDR_OK;
 }

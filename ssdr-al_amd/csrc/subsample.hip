@@ -544,6 +544,7 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
                           float* d_op, float* d_of, int32_t* d_oc, int64_t* d_om, GsParams* prm, hipStream_t s, const float* centres, size_t num_points);
 int frontend_tile_stats(hipStream_t s, int32_t* stage, int32_t* reduced, int32_t* buckets, size_t nr);
 void frontend_tile_forget(hipStream_t s);
+int frontend_scatter_stats(hipStream_t s, int64_t* scattered, int64_t* points, size_t nr);
 
 // centres (host [nr, 3]) / num_points: the partition path may leave out the buckets that cannot hold one of the num_points rows nearest to a room's centre
 // (ssdr_tile_from_rooms_batch_dev); NULL: every row of every cloud
@@ -671,6 +672,14 @@ int ssdr_tile_from_rooms_stats(void* stream, int32_t* out_stage, int32_t* out_re
     if (num_clouds == 0 || num_clouds > RADIX_MAX_SEG) { set_error("tile_from_rooms_stats: bad arguments"); return SSDR_ERR_INVALID; }
     SSDR_TRY(ensure_init());
     return frontend_tile_stats(pick_stream(stream), out_stage, out_reduced, out_buckets, num_clouds);
+}
+
+/* The records the partition of the last ssdr_tile_from_rooms_batch_dev on `stream` wrote (waits for it), per cloud (int64 [num_clouds] each, may be NULL), and the
+ * cloud's points: fewer records than points = the scatter left out the buckets no stage opened. */
+int ssdr_tile_from_rooms_scatter_stats(void* stream, int64_t* out_scattered, int64_t* out_points, size_t num_clouds) {
+    if (num_clouds == 0 || num_clouds > RADIX_MAX_SEG) { set_error("tile_from_rooms_scatter_stats: bad arguments"); return SSDR_ERR_INVALID; }
+    SSDR_TRY(ensure_init());
+    return frontend_scatter_stats(pick_stream(stream), out_scattered, out_points, num_clouds);
 }
 
 /* which implementation ssdr_grid_subsample_batch_dev uses: SSDR_SUBSAMPLE_AUTO (default: the bucket partition of frontend.hip for rows of at most 7 words,

@@ -130,6 +130,7 @@ def lib():
         L.ssdr_tile_select_batch_dev.argtypes = [vp, vp, i32, vp, vp, sz, vp, sz, vp, vp, f32, vp, vp, vp, vp, vp, vp]
         L.ssdr_tile_from_rooms_batch_dev.argtypes = [vp, vp, sz, vp, sz, vp, sz, f32, vp, vp, vp, vp, vp, sz, vp, vp, f32, vp, vp, vp, vp, vp]
         L.ssdr_tile_from_rooms_stats.argtypes = [vp, vp, vp, vp, sz]
+        L.ssdr_tile_from_rooms_scatter_stats.argtypes = [vp, vp, vp, sz]
         L.ssdr_tile_select_possibility_dev.argtypes = [vp, vp, i32, vp, sz, vp, sz, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp]
         L.ssdr_split3_dev.argtypes = [vp, sz, sz, sz, sz, vp, vp, vp, sz, C.POINTER(sz), vp]
         L.ssdr_chamfer3d_forward_dev.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]
