@@ -828,6 +828,37 @@ int ssdr_bn_stats_merge_dev(const float* d_records, int world, int C, float* d_m
 int ssdr_rank_sums_merge_dev(const float* d_records, int world, int n, float* d_out, void* stream);
 int ssdr_randla_train_dropout_mask_range_dev(uint64_t seed, uint64_t step, uint64_t first, size_t n, uint8_t* d_mask, void* stream);
 
+/* ---- per-row draws of the tile generators, made on the device (csrc/draw.hip) ----
+ * Every value is a pure function of a counter (seed u64, epoch u32, step u32, kind u32, element u64, word u32); nothing depends on the launch.
+ * All arithmetic is on uint32, modulo 2^32:
+ *   mix32(x):   x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16          (the dropout mask's mixer)
+ *   state(c):   s = mix32(lo32(seed) ^ c); s = mix32(s ^ hi32(seed)); s = mix32(s ^ epoch); s = mix32(s ^ step); s = mix32(s ^ kind)
+ *   chain(c, e, j): a = mix32(state(c) ^ lo32(e)); a = mix32(a + hi32(e)); a = mix32(a ^ j)
+ *   word(e, j): mix32(chain(0x9e3779b9, e, j) + chain(0x85ebca6b, e, j))
+ * Two chains, because one alone is a bijection of lo32(e): a tile's keys would be one fixed bijection of an aligned block of integers.
+ *   bits53(e, j): (word(e, j) >> 5) * 2^26 + (word(e, j + 1) >> 6), an integer in [0, 2^53)
+ * ssdr_draw_perm_dev: d_perm i32 [num_tiles, num_points]; row t is the stable argsort over r < num_points of
+ *   key(T, r) = word(T * 2^32 + r, 0) >> (32 - key_bits) with T = first_tile + t and kind = SSDR_DRAW_PERM: ascending key, equal keys by ascending r.
+ *   key_bits = 32 is the generators' choice (smaller values force ties).  first_tile: tiles [first_tile, first_tile + num_tiles) of a larger
+ *   call, row for row.  Refused before anything is launched: NULL, num_tiles or num_points 0, key_bits outside 1 .. 32, a tile id of 2^32 or
+ *   more (SSDR_ERR_INVALID); more than 0x3fffffff pairs in the sort buffers, where every tile of more than 1024 rows owns its rows rounded up to a
+ *   multiple of 2048 and smaller tiles are packed, up to 65536 together, and rounded up likewise (SSDR_ERR_UNSUPPORTED).
+ * ssdr_draw_uniform_dev: d_out f32 [n], d_out[i] = (word(first + i, 0) >> 8) * 2^-24, in [0, 1 - 2^-24] (the rule of NumPy's float32 random).
+ * ssdr_draw_normal_dev: d_out f64 [n], d_out[i] = scale * z(first + i) by Box-Muller in float64, every product and call rounded on its own:
+ *   u1 = (bits53(e, 0) + 1) * 2^-53 in (0, 1], u2 = bits53(e, 2) * 2^-53 in [0, 1), z = sqrt(-2 * log(u1)) * cos(6.283185307179586 * u2).
+ *   log and cos are the platform's: builds agree to a few units in the last place, not bit for bit.
+ * first makes a rank's draws the slice of the union's, as ssdr_randla_train_dropout_mask_range_dev does.  Both refuse NULL and n = 0 (SSDR_ERR_INVALID).
+ * The generators use element = tile * num_points + r for SSDR_DRAW_DUP and (tile * num_points + r) * 3 + axis for SSDR_DRAW_AUG_NOISE.
+ * All three only enqueue; the host reads no device value; the permutation's sort scratch is kept per stream. */
+#define SSDR_DRAW_PERM 0
+#define SSDR_DRAW_DUP 1
+#define SSDR_DRAW_AUG_NOISE 2
+int ssdr_draw_perm_dev(uint64_t seed, uint32_t epoch, uint32_t step, uint64_t first_tile, size_t num_tiles, size_t num_points, int key_bits,
+                       int32_t* d_perm, void* stream);
+int ssdr_draw_uniform_dev(uint64_t seed, uint32_t epoch, uint32_t step, uint32_t kind, uint64_t first, size_t n, float* d_out, void* stream);
+int ssdr_draw_normal_dev(uint64_t seed, uint32_t epoch, uint32_t step, uint32_t kind, uint64_t first, size_t n, double scale, double* d_out,
+                         void* stream);
+
 /* ---- plain device memory for callers without their own allocator (tests, the ctypes mirror) ---------- */
 int ssdr_dev_alloc(size_t bytes, void** d_ptr);
 int ssdr_dev_free(void* d_ptr);

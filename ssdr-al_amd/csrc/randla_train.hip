@@ -19,6 +19,7 @@
 #include "ssdr_internal.hpp"
 #include "scatter_det.hpp"
 #include "train_exchange.hpp"
+#include "mix32.hpp"
 #include <cmath>
 #include <cstring>
 #include <functional>
@@ -322,8 +323,7 @@ __global__ void pool_bwd_kernel(const float* src, float* dsrc, int lds, int src_
         }
 }
 
-// ---- dropout (keep_prob 0.5 after fc2, RandLANet.py:176-177) ----
-__device__ inline uint32_t mix32(uint32_t x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; }
+// ---- dropout (keep_prob 0.5 after fc2, RandLANet.py:176-177); mix32: mix32.hpp ----
 // mask[i] = the bit of element first + i
 __global__ void dropout_mask_kernel(uint64_t seed, uint64_t step, uint64_t first, long n, uint8_t* mask) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

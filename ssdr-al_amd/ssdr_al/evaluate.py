@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import draws as device_draws
 from ._lib import DevArray
 from .knn import knn
 
@@ -80,14 +81,23 @@ class VoteTester:
     per-cloud minima and test_probs.  The host draws the randomness (initial map from (seed, cloud), noise / shuffle / padding
     draws from (seed, epoch, step)), reads the cloud minima once per epoch and the final matrices, nothing else.
 
+    ``draws="device"``: the per-row draws (the shuffle permutations, the padding draws) are made on the device from the counter
+    (seed, epoch, step, kind, element) instead (``ssdr_al.draws``); ``draw`` then returns the per-tile noise
+    alone and nothing per row is uploaded.  The rule is per key: a per-row entry that a ``draws=`` callable does return is uploaded.
+
     The generator chain (ssdr_vote_tiles_dev) runs on a stream of its own, DEPTH batches ahead of the network at most (the tile
     and draw buffers exist DEPTH times); the draws are uploaded on a third stream, so the host waits for the generator of DEPTH
-    batches ago only, never for the network."""
+    batches ago only, never for the network.  ``ready`` guards the draw buffers against the upload
+    stream.  A draw made on the device needs no event of its own: it is enqueued on the generator's stream in front of the chain,
+    the stream whose chain was the last reader of those buffers, and the set's next upload waits for ``ready`` as before."""
 
     DEPTH = 2
 
-    def __init__(self, weights, clouds, config=None, precision="f32", seed=0, num_votes=100, test_smooth=0.95, possibility=None):
+    def __init__(self, weights, clouds, config=None, precision="f32", seed=0, num_votes=100, test_smooth=0.95, possibility=None, draws="host"):
         from . import randlanet
+        if draws not in ("host", "device"):
+            raise ValueError("VoteTester: draws must be 'host' or 'device'")
+        self.draws = draws
         from .helper_tool import ConfigS3DIS
         cfg = self.cfg = ConfigS3DIS if config is None else config
         L = _lib.lib()
@@ -166,30 +176,42 @@ class VoteTester:
         except Exception:
             pass
 
-    # ---- randomness (host, as everywhere) -------------------------------------------------------------------------------
+    # ---- randomness (host; draws="device": the per-tile entries only) -----------------------------------------------------
     def draw(self, epoch, step):
         """the draws of one batch from (seed, epoch, step): noise [B,3] = normal(0, noise_init / 10) cast to float32 (test.py:114-115), one shuffle
-        permutation per tile (DP.shuffle_idx, :125), the padding draws of data_aug (:137-141; zeros when no cloud is smaller than a tile)"""
+        permutation per tile (DP.shuffle_idx, :125), the padding draws of data_aug (:137-141; zeros when no cloud is smaller than a tile).
+        draws="device": the noise alone."""
         rng = np.random.default_rng([self.seed, int(epoch), int(step)])
         noise = rng.normal(scale=self.cfg.noise_init / 10, size=(self.B, 3)).astype(np.float32)
+        if self.draws == "device":
+            return dict(noise=noise)
         perm = np.stack([rng.permutation(self.N) for _ in range(self.B)]).astype(np.int32)
         dup = rng.random((self.B, self.N), dtype=np.float32) if self.pads else None
         return dict(noise=noise, perm=perm, dup=dup)
 
     # ---- the two halves of a batch, both enqueue-only ---------------------------------------------------------------------
-    def _generate(self, draws):
-        """get_batch (test.py:97-151) of the next batch on the generator's stream, into buffer set (batch % DEPTH)"""
+    def _generate(self, draws, epoch=None, step=None):
+        """get_batch (test.py:97-151) of the next batch on the generator's stream, into buffer set (batch % DEPTH).  epoch, step: the counter of
+        the per-row draws made on the device (default: the batch about to run)"""
         if self.nc == 0:
             raise ValueError("VoteTester: no clouds")
         L = _lib.lib()
         st = self.sets[self._issued % self.DEPTH]
         if st["gen_used"]:
             _lib.check(L.ssdr_stream_wait_event(self.s_up, st["ready"]))       # the draws of DEPTH batches ago have been read
-        ups = [("noise", np.float32), ("perm", np.int32)] + ([("dup", np.float32)] if draws.get("dup") is not None else [])
+        on_device = self.draws == "device"
+        ups = [("noise", np.float32)] + ([("perm", np.int32)] if not on_device or draws.get("perm") is not None else [])
+        ups += [("dup", np.float32)] if draws.get("dup") is not None else []
         for k, dt in ups:
             a = np.ascontiguousarray(draws[k], dt)
             assert a.shape == st[k].shape, (k, a.shape, st[k].shape)
             _lib.check(L.ssdr_memcpy_h2d_on(st[k].ptr, _lib.ptr(a), a.nbytes, self.s_up))      # waits for the upload stream alone
+        if on_device:         # the per-row entries the dict does not hold: same stream as their last reader, no event
+            epoch, step = self.epochs if epoch is None else epoch, self._step_in_epoch if step is None else step
+            if draws.get("perm") is None:
+                device_draws.perm(self.seed, epoch, step, self.B, self.N, out=st["perm"], stream=self.s_gen)
+            if draws.get("dup") is None and self.pads:
+                device_draws.uniform(self.seed, epoch, step, device_draws.DUP, self.B * self.N, out=st["dup"], stream=self.s_gen)
         if st["net_used"]:
             _lib.check(L.ssdr_stream_wait_event(self.s_gen, st["consumed"]))   # the tile buffers' last reader
         _lib.check(L.ssdr_vote_tiles_dev(self.d_points.ptr, self.d_colors.ptr, 3, self.d_labels.ptr if self.has_labels else None, self.d_poss.ptr,
@@ -233,7 +255,7 @@ class VoteTester:
         self._drain()
         if draws is None:
             draws = self.draw(self.epochs, self._step_in_epoch)
-        self._generate(draws)
+        self._generate(draws, self.epochs, self._step_in_epoch)
         st = self._network()
         self._step_in_epoch += 1
         _lib.sync(self.s_gen)
@@ -246,7 +268,7 @@ class VoteTester:
         gen = net = self._step_in_epoch
         while net < self.steps:
             while gen < self.steps and gen - net < self.DEPTH:
-                self._generate(self.draw(self.epochs, gen) if draws is None else draws(self.epochs, gen))
+                self._generate(self.draw(self.epochs, gen) if draws is None else draws(self.epochs, gen), self.epochs, gen)
                 gen += 1
             self._network()
             net += 1

@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import draws as device_draws
 from ._lib import DevArray
 
 XY_ONLY, GLOBAL_ROWS = 1, 2          # SSDR_FEED_*
@@ -78,12 +79,21 @@ class TrainFeeder:
     alone: the upload stream waits for the set's previous ``ready`` event before it overwrites them.  The batch arrays (everything a FeedBatch hands out,
     cloud_idx and the centres included) are written by the generator alone: its stream waits for the set's ``consumed`` event first, so nothing a consumer
     may still read is touched before the consumer's stream has run what it had enqueued at ``release``.  ``next_batch(stream)`` hands out the oldest generated batch (None at
-    the end of an epoch); ``for batch in feeder.epoch_batches(stream)`` does the same."""
+    the end of an epoch); ``for batch in feeder.epoch_batches(stream)`` does the same.
+
+    ``draws="device"``: the per-row draws (shuffle permutations, padding draws, augmentation noise) are made on the device from the counter
+    (seed, epoch, step, kind, element) instead (``ssdr_al.draws``); ``draw`` then returns the per-tile entries alone and nothing
+    per row is uploaded.  The rule is per key: a per-row entry that a ``draws=`` callable does return is uploaded.  A draw made on the device needs
+    no event of its own: it is enqueued on the generator's stream in front of the chain, the stream whose chain was the last reader of those
+    buffers, and the set's next upload waits for ``ready`` as before."""
 
     DEPTH = 2
 
-    def __init__(self, clouds, pseudo_gt, config=None, dataset="S3DIS", seed=0, possibility=None, class_weight=None, color_scale=1.0):
+    def __init__(self, clouds, pseudo_gt, config=None, dataset="S3DIS", seed=0, possibility=None, class_weight=None, color_scale=1.0, draws="host"):
         from .helper_tool import ConfigS3DIS, ConfigSemantic3D
+        if draws not in ("host", "device"):
+            raise ValueError("TrainFeeder: draws must be 'host' or 'device'")
+        self.draws = draws
         if dataset not in ("S3DIS", "Semantic3D"):
             raise ValueError("TrainFeeder: dataset must be 'S3DIS' or 'Semantic3D'")
         self.dataset = dataset
@@ -187,7 +197,7 @@ class TrainFeeder:
         except Exception:
             pass
 
-    # ---- randomness (host, as everywhere) -------------------------------------------------------------------------------
+    # ---- randomness (host; draws="device": the per-tile entries only) -----------------------------------------------------
     def order(self, epoch):
         """S3DIS: the DataLoader's permutation of the clouds for this epoch"""
         return np.random.default_rng([self.seed, int(epoch)]).permutation(self.nc).astype(np.int32)
@@ -200,12 +210,14 @@ class TrainFeeder:
         per tile, the padding draws (None when no cloud is smaller than a tile).  S3DIS: cloud [b] (the epoch's order) and point [b] = randint(n_c)
         (s3dis_dataset.py:119).  Semantic3D: rot [b,2] = (cos, sin) of theta = uniform(0, 2 pi), scale [b,3] = uniform(scale_min, scale_max) (one
         value for all axes unless anisotropic) times the symmetry signs, aug_noise float64 [b,N,3] = normal(0, augment_noise) or None when that is 0
-        (semantic3d_dataset_train.py:240-272)."""
+        (semantic3d_dataset_train.py:240-272).  draws="device": without perm, dup and aug_noise."""
         rng = np.random.default_rng([self.seed, int(epoch), int(step)])
         b, N, cfg = self.batch_size_of(step), self.N, self.cfg
-        d = dict(noise=rng.normal(scale=cfg.noise_init / 10, size=(b, 3)).astype(np.float32),
-                 perm=np.stack([rng.permutation(N) for _ in range(b)]).astype(np.int32),
-                 dup=rng.random((b, N), dtype=np.float32) if self.pads else None)
+        host = self.draws == "host"
+        d = dict(noise=rng.normal(scale=cfg.noise_init / 10, size=(b, 3)).astype(np.float32))
+        if host:
+            d.update(perm=np.stack([rng.permutation(N) for _ in range(b)]).astype(np.int32),
+                     dup=rng.random((b, N), dtype=np.float32) if self.pads else None)
         if self.dataset == "S3DIS":
             cloud = self.order(epoch)[step * self.B: step * self.B + b]
             d.update(cloud=cloud, point=np.array([rng.integers(0, self.sizes[c]) for c in cloud], np.int32))
@@ -217,8 +229,9 @@ class TrainFeeder:
             for i, on in enumerate(getattr(cfg, "augment_symmetries", [False, False, False])):
                 if on:
                     sym[:, i] = np.round(rng.uniform(size=b)) * 2 - 1
-            d.update(rot=np.stack([np.cos(theta), np.sin(theta)], axis=1), scale=s * sym,
-                     aug_noise=rng.normal(scale=self.augment_noise, size=(b, N, 3)) if self.augment_noise != 0 else None)
+            d.update(rot=np.stack([np.cos(theta), np.sin(theta)], axis=1), scale=s * sym)
+            if host:
+                d.update(aug_noise=rng.normal(scale=self.augment_noise, size=(b, N, 3)) if self.augment_noise != 0 else None)
         return d
 
     # ---- the generator: enqueue only --------------------------------------------------------------------------------------
@@ -228,7 +241,9 @@ class TrainFeeder:
         b, N = len(draws["noise"]), self.N
         if st["gen_used"]:
             _lib.check(L.ssdr_stream_wait_event(self.s_up, st["ready"]))       # the draws of DEPTH batches ago have been read
-        ups = [("noise", np.float32), ("perm", np.int32)] + ([("dup", np.float32)] if draws.get("dup") is not None else [])
+        on_device = self.draws == "device"
+        ups = [("noise", np.float32)] + ([("perm", np.int32)] if not on_device or draws.get("perm") is not None else [])
+        ups += [("dup", np.float32)] if draws.get("dup") is not None else []
         ups += [("tile_cloud", np.int32), ("point", np.int32)] if self.dataset == "S3DIS" else [("rot", np.float64), ("scale", np.float64)]
         if draws.get("aug_noise") is not None:
             if st.get("aug_noise") is None:
@@ -238,6 +253,15 @@ class TrainFeeder:
             a = np.ascontiguousarray(draws["cloud" if k == "tile_cloud" else k], dt)
             assert a.shape == (b,) + st[k].shape[1:], (k, a.shape, st[k].shape)
             _lib.check(L.ssdr_memcpy_h2d_on(st[k].ptr, _lib.ptr(a), a.nbytes, self.s_up))      # waits for the upload stream alone
+        noisy = draws.get("aug_noise") is not None
+        if on_device:         # the per-row entries the dict does not hold: same stream as their last reader, no event
+            if draws.get("perm") is None:
+                device_draws.perm(self.seed, epoch, step, b, N, out=st["perm"], stream=self.s_gen)
+            if draws.get("dup") is None and self.pads:
+                device_draws.uniform(self.seed, epoch, step, device_draws.DUP, b * N, out=st["dup"], stream=self.s_gen)
+            if not noisy and self.augment_noise != 0:
+                device_draws.normal(self.seed, epoch, step, device_draws.AUG_NOISE, b * N * 3, scale=self.augment_noise, out=st["aug_noise"], stream=self.s_gen)
+                noisy = True
         if st["wait_consumed"]:
             _lib.check(L.ssdr_stream_wait_event(self.s_gen, st["consumed"]))   # the buffers' last reader
             st["wait_consumed"] = False
@@ -252,7 +276,7 @@ class TrainFeeder:
                                              _lib.ptr(self.off), self.nc, b, N, st["noise"].ptr, st["perm"].ptr, st["dup"].ptr, self.color_scale,
                                              xyz0.ptr, st["feat"].ptr, st["idx"].ptr, st["labels"].ptr, st["cloud"].ptr, st["center"].ptr,
                                              XY_ONLY, self.d_cw.ptr, len(self.class_weight), self.d_act.ptr, self.d_pse.ptr, st["act"].ptr, st["pse"].ptr, s))
-            an = st["aug_noise"].ptr if draws.get("aug_noise") is not None else None
+            an = st["aug_noise"].ptr if noisy else None
             _lib.check(L.ssdr_feed_augment_dev(xyz0.ptr, b, N, st["rot"].ptr, st["scale"].ptr, an, 3, st["feat"].ptr, s))
         arr = C.c_void_p * self.L
         r = np.asarray(self.cfg.sub_sampling_ratio[: self.L], np.int32)
