@@ -73,13 +73,14 @@ __global__ __launch_bounds__(256) void sel_region_stats(const float* __restrict_
         double r;
         if (mode == 0) {
             const float sum = np_pairwise<float>([&](int j) { return unc[sp_pts[lo + j]]; }, n);
-            r = (double)(float)((double)sum / (double)n);
+            r = (double)(float)((double)(sum + 0.f) / (double)n);          // identity + pairwise: see sel_region_stats_w
         } else if (mode == 1) {                                      // weights_percentage (:92-100) * uncertainty
             r = np_pairwise<double>([&](int j) { const int p = sp_pts[lo + j]; return ((double)h[cls[p]] / (double)n) * (double)unc[p]; }, n);
+            r = r + 0.0;
         } else {                                                     // WetSU (:19-26)
             const double a = np_pairwise<double>([&](int j) { const int p = sp_pts[lo + j]; return (double)unc[p] * (cls[p] == d ? 1.0 : 0.0); }, n);
             const double b = np_pairwise<double>([&](int j) { const int p = sp_pts[lo + j]; return (double)unc[p] * (1.0 - (cls[p] == d ? 1.0 : 0.0)); }, n);
-            r = a - b;
+            r = (a + 0.0) - (b + 0.0);
         }
         region_unc[s] = r;
     }
@@ -151,23 +152,26 @@ __global__ __launch_bounds__(256) void sel_region_stats_w(const float* __restric
                     da = base == 0 ? sa : da + sa; db = base == 0 ? sb : db + sb;
                 }
             }
-            r = mode == 0 ? (double)(float)((double)fa / (double)n) : mode == 1 ? da : da - db;
+            r = mode == 0 ? (double)(float)((double)(fa + 0.f) / (double)n) : mode == 1 ? da + 0.0 : (da + 0.0) - (db + 0.0);      // + 0: see below
         } else if (mode == 0) {
+            // np.sum / np.mean are identity + pairwise(...): the finished sum plus T(0).  It changes one value, a sum of -0.0 terms alone (the entropy of one-hot
+            // rows), which the eight accumulators started from the first terms leave at -0.0 and NumPy returns as +0.0
             float sum = 0.f;
             if (w8) sum = np_pairwise_wave<float>([&](int j) { return U(j); }, n, lane);
             else if (lane == 0) sum = np_pairwise<float>([&](int j) { return U(j); }, n);
-            r = (double)(float)((double)sum / (double)n);
+            r = (double)(float)((double)(sum + 0.f) / (double)n);
         } else if (mode == 1) {                                      // weights_percentage (:92-100) * uncertainty
             auto term = [&](int j) { return ((double)h[K(j)] / (double)n) * (double)U(j); };
             if (w8) r = np_pairwise_wave<double>(term, n, lane);
             else if (lane == 0) r = np_pairwise<double>(term, n);
+            r = r + 0.0;
         } else {                                                     // WetSU (:19-26)
             auto ta = [&](int j) { return (double)U(j) * (K(j) == d ? 1.0 : 0.0); };
             auto tb = [&](int j) { return (double)U(j) * (1.0 - (K(j) == d ? 1.0 : 0.0)); };
             double a = 0.0, b = 0.0;
             if (w8) { a = np_pairwise_wave<double>(ta, n, lane); b = np_pairwise_wave<double>(tb, n, lane); }
             else if (lane == 0) { a = np_pairwise<double>(ta, n); b = np_pairwise<double>(tb, n); }
-            r = a - b;
+            r = (a + 0.0) - (b + 0.0);
         }
         if (lane == 0) region_unc[s] = r;
         wave_sync();
@@ -234,12 +238,16 @@ __global__ __launch_bounds__(256) void sel_clsbal(const int* __restrict__ region
 }
 
 // ---- ranking: argsort(-u) (sampler2.py:640), ties by ascending index --------------------------------------------
+// The order-preserving map of -u to u64, with NumPy's two rules for what IEEE bits alone order differently: +0.0 and -0.0 are EQUAL (0.0 - u is +0.0 for
+// both, where -u keeps two bit patterns one key apart), and every NaN, whatever its sign bit, ranks LAST (one key above -u = +inf's 0xfff0...0; not all
+// ones: sel_rank_count adds 1 to a key).  Equal keys go by ascending index in both rankers.
+__device__ __forceinline__ unsigned long long rank_key(double u) {
+    if (u != u) return 0xfffffffffffffffeull;
+    const unsigned long long b = (unsigned long long)__double_as_longlong(0.0 - u);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
 __global__ __launch_bounds__(256) void sel_rank_keys(const double* __restrict__ u, int S, uint64_t* keys, uint32_t* vals) {
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < S; i += gridDim.x * 256) {
-        unsigned long long b = (unsigned long long)__double_as_longlong(-u[i]);
-        b = (b >> 63) ? ~b : (b | 0x8000000000000000ull);            // order-preserving map of IEEE doubles to u64
-        keys[i] = b; vals[i] = (uint32_t)i;
-    }
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < S; i += gridDim.x * 256) { keys[i] = rank_key(u[i]); vals[i] = (uint32_t)i; }
 }
 
 // Ranking of up to RANK_SMALL regions by COUNTING, spread over the chip: the rank of region i is the number of regions whose (key, index) pair is
@@ -251,17 +259,14 @@ constexpr int RANK_SMALL = 8192;
 __global__ __launch_bounds__(256) void sel_rank_count(const double* __restrict__ u, int S, int* __restrict__ sorted_inds) {
     __shared__ unsigned long long s_k[RANK_SMALL];
     const int tid = threadIdx.x;
-    for (int i = tid; i < S; i += 256) {
-        unsigned long long b = (unsigned long long)__double_as_longlong(-u[i]);
-        s_k[i] = (b >> 63) ? ~b : (b | 0x8000000000000000ull);          // order-preserving map of IEEE doubles to u64 (as sel_rank_keys)
-    }
+    for (int i = tid; i < S; i += 256) s_k[i] = rank_key(u[i]);
     __syncthreads();
     const int i = blockIdx.x * 32 + (tid >> 3), part = tid & 7;
     const bool live = i < S;
     const unsigned long long ki = s_k[live ? i : 0];
     int cnt = 0;
     if (live) {
-        // (kj, j) < (ki, i)  <=>  kj < ki + (j < i): one 64-bit add and compare per pair (ki + 1 does not wrap: only a NaN maps to all ones); eight
+        // (kj, j) < (ki, i)  <=>  kj < ki + (j < i): one 64-bit add and compare per pair (ki + 1 does not wrap: the largest key, a NaN's, is all ones minus one); eight
         // LDS reads in flight
         int j = part;
         for (; j + 56 < S; j += 64) {

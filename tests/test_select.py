@@ -361,9 +361,10 @@ def test_selection_fresh_inputs_against_oracle(backend):
     assert np.array_equal(u, O.point_uncertainty(prob, "sb"))
     ru, dom, cnt = sampler.compute_region_stats(u, cls, off, pts, C, ["WetSU"])
     eru, edom, ecnt = O.region_stats(u, cls, off, pts, C, "WetSU")
-    assert np.array_equal(ru, eru) and np.array_equal(dom, edom) and np.array_equal(cnt, ecnt)
+    b64 = lambda a: np.ascontiguousarray(a, np.float64).view(np.uint64)          # on the bits: np.array_equal cannot see the sign of a zero
+    assert np.array_equal(b64(ru), b64(eru)) and np.array_equal(dom, edom) and np.array_equal(cnt, ecnt)
     for mode in ("mean", "sum_weight"):                     # NumPy's pairwise order in every mode, for every size class
-        assert np.array_equal(sampler.compute_region_stats(u, cls, off, pts, C, [mode])[0], O.region_stats(u, cls, off, pts, C, mode)[0]), mode
+        assert np.array_equal(b64(sampler.compute_region_stats(u, cls, off, pts, C, [mode])[0]), b64(O.region_stats(u, cls, off, pts, C, mode)[0])), mode
     sel = O.rank_regions(ru)[:40].astype(np.int32)
     mf = sampler.segment_mean_features(feat, cls, dom, off, pts, sel)
     sub_off = np.concatenate([[0], np.cumsum(off[sel + 1] - off[sel])]).astype(np.int32)
