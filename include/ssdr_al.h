@@ -211,6 +211,31 @@ int ssdr_tile_from_rooms_stats(void* stream, int32_t* out_stage, int32_t* out_re
  * part of its buckets, records == points for a cloud that went on to a later stage or was reduced whole.  -1 / -1 when the call took the sort; records -1 under
  * SSDR_FE_SCATTER_PRUNE=0 (development: the one scatter of every record, which does not count). */
 int ssdr_tile_from_rooms_scatter_stats(void* stream, int64_t* out_scattered, int64_t* out_points, size_t num_clouds);
+/* Room plans: a caller that uploads a set of rooms once and draws many tiles from it (every tile has its own centres) builds a plan behind the upload and
+ * hands it to every call.  The plan keeps what the partition path derives from the points and sampleDl alone — every cloud's grid and bucket geometry, its status
+ * bits, the per-chunk and per-bucket point counts with their prefix sums, one work item per non-empty bucket — in device buffers of its own; a planned call reads
+ * them and starts at the order of the buckets around the centres (two of the three reads of all coordinates and five launches fewer per call).
+ *   ssdr_rooms_plan_create_dev   builds the plan on `stream` (asynchronous; the inputs as for ssdr_tile_from_rooms_batch_dev).  Rows of more than 7 words
+ *                                (3 + fdim + ldim) take the sort, which keeps nothing: SSDR_ERR_UNSUPPORTED.
+ *   ssdr_tile_from_rooms_planned_batch_dev   ssdr_tile_from_rooms_batch_dev with the plan: the same outputs, ssdr_grid_subsample_status and
+ *                                ssdr_tile_from_rooms_*stats bit for bit, refused clouds (status bits 2, 4) and clouds reduced whole included.  It may run on any
+ *                                stream: the first call on a stream other than the plan's is ordered behind the build by an event the plan keeps.  SSDR_ERR_INVALID
+ *                                when d_points, d_features, d_classes, fdim, ldim, cloud_offsets, num_clouds or sampleDl differ from the plan's.  Under
+ *                                SSDR_SUBSAMPLE_SORT the plan is checked and not used.
+ *   ssdr_rooms_plan_destroy      waits for the device, then frees the plan (NULL is accepted).
+ * CONTRACT: a plan is valid while the bytes behind d_points and cloud_offsets are unchanged.  The library compares pointers and offsets, not the points: a caller
+ * that rewrites the points in place destroys the plan and creates it again.  (Features and classes are not part of the plan's tables; their pointers are
+ * compared so that a plan stands for one uploaded set.)  A plan is read-only once built: any number of planned calls, on any streams, may share it.
+ * Memory: the per-chunk counts are sized for the worst case, 16384 buckets x ceil(largest cloud / 32768) chunks x num_clouds words — about 39 MB for 16 clouds
+ * of up to 1.2 M points — plus 0.7 MB per cloud of bucket tables, per plan. */
+int ssdr_rooms_plan_create_dev(const float* d_points, const float* d_features, size_t fdim, const int32_t* d_classes, size_t ldim,
+                               const int64_t* cloud_offsets, size_t num_clouds, float sampleDl, void* stream, void** out_plan);
+int ssdr_rooms_plan_destroy(void* plan);
+int ssdr_tile_from_rooms_planned_batch_dev(const void* plan, const float* d_points, const float* d_features, size_t fdim, const int32_t* d_classes, size_t ldim,
+                                           const int64_t* cloud_offsets, size_t num_clouds, float sampleDl,
+                                           float* d_sub_points, float* d_sub_features, int32_t* d_sub_classes, int64_t* d_sub_m,
+                                           const float* centers, size_t num_points, const int32_t* d_perm, const float* d_dup_u, float color_scale,
+                                           float* d_out_xyz, float* d_out_feat, int32_t* d_out_idx, int32_t* d_out_labels, void* stream);
 /* Test-time variant (S3/s3dis_dataset_test.py:105-143): the same tile, plus the possibility-map update
  * possibility[idx] += (1 - dists/max(dists))^2 over the tile's (un-padded) points (float64 map, float32 dists) and,
  * optionally, min / argmin of the updated map (the next pick: :106-108).  An empty cloud (*d_m <= 0): the tile outputs and the

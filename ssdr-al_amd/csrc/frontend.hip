@@ -25,12 +25,14 @@
 // HBM traffic: 12 N (minmax) + 12 N (count) + 28 N + 32 N (scatter) + 32 N + 32 M (reduce) + 32 M + 28 M (move) bytes for N points and M
 // voxels, against 28 (N + M) algorithmic.  The staged reduction of ssdr_tile_from_rooms_batch_dev (below) orders a room's buckets BEFORE the scatter and writes and
 // reduces only the share p of the points that lies in stage 1's buckets: 12 N + 12 N + 28 N + 32 p N (scatter) + 32 p N + 32 p M (reduce) + (32 + 28) p M (move);
-// p = 0.42 on the bench's rooms.  A room that goes on to stage 2 pays 28 N more (a second read of its points) for the other 32 (1 - p) N of records.  Clouds whose grid does not fit (more than FE_NBMAX buckets of 1024 voxels) or that
+// p = 0.42 on the bench's rooms.  A room that goes on to stage 2 pays 28 N more (a second read of its points) for the other 32 (1 - p) N of records.  A call with a room
+// plan (FePlan) starts at the order: the 12 N + 12 N of minmax and count were paid once, when the plan was built.  Clouds whose grid does not fit (more than FE_NBMAX buckets of 1024 voxels) or that
 // hold a voxel of more than FE_CAP points are flagged (ssdr_grid_subsample_status) and belong to the sort-based entry point.
 #include "ssdr_internal.hpp"
 #include "block_prims.hpp"
 #include "voxel_label.hpp"
 #include "subsample_types.hpp"
+#include <memory>
 
 namespace ssdr {
 namespace {
@@ -216,6 +218,14 @@ __global__ __launch_bounds__(FE_NT) void fe_bscan(FeTab t, const FeGeom* __restr
         __syncthreads();
     }
     if (tid == 0) bo[g.nb] = (unsigned)(carry >> 20);
+}
+
+// A call with a room plan: what fe_params and fe_bscan leave per call, from the plan (one workgroup per cloud).  The per-call counters start as fe_params
+// starts them, with the whole-room item count fe_bscan reached, and the caller's prm as fe_params / fe_count left it (m = 0, the status bits, the grid).
+__global__ __launch_bounds__(64) void fe_plan_begin(const GsParams* __restrict__ plan_prm, const int* __restrict__ plan_counters, GsParams* prm, int* counters) {
+    const int r = blockIdx.x, tid = threadIdx.x;
+    if (r == 0) counters[tid] = tid == 0 ? plan_counters[0] : 0;
+    if (tid == 0) { fe_scatter_counters(counters)[r] = 0ull; prm[r] = plan_prm[r]; }
 }
 
 // second read of the points: packed records behind the LDS cursors of this chunk, FE_PPT points per thread and step (their loads issued
@@ -761,7 +771,10 @@ __global__ __launch_bounds__(BS) void fe_move(FeMoveArgs a) {
 //   2  ranks [K1, K2): K2 = the first rank at which the cumulative points reach 1.15 rho num_points, widened in the same way; if the check fails again
 //   3  ranks [K2, n): the rest of the room (also what a room of fewer than num_points voxels ends with: the tile's padding branch).
 // Unreduced buckets read as empty (nocc, lrc = 0) to fe_rowpre / fe_move: the rows that exist keep their key order, so the tile's tie rule
-// (distance, then row) is the same relation on them.  Nothing is kept between calls; the set of reduced buckets is a function of the inputs.
+// (distance, then row) is the same relation on them.  The set of reduced buckets is a function of the inputs.  A call without a room plan keeps nothing
+// between calls.  A room plan (FePlan, below) keeps what minmax / params / count / colscan / bscan leave — geom, cntm, tot, boff, the whole-room items and
+// their count, every room's status and grid parameters — which is a function of the rooms' points and dl alone: a call with a plan reads those tables and
+// writes none of them; everything that depends on the centres (the order, the flags, the records, nocc / lrc / trow, the rows) stays per call.
 constexpr int FE_TO_NMAX = 8192;     // non-empty buckets of a room the order is sorted for (one LDS word each); a room with more is reduced whole
 constexpr int FE_TO_KBITS = 14;      // low bits of a sort word: the bucket (FE_NBMAX = 2^14); above them 18 bits of the least distance's pattern
 static_assert(FE_NBMAX == 1 << FE_TO_KBITS, "bucket bits of the order's sort words");
@@ -977,18 +990,9 @@ struct FeState {
     DevBuf flag; bool pruned = false; std::vector<long long> room_n;      // [room][FE_NBMAX] bytes: stage 1 reduces this bucket; the last staged call: pruned scatter? its rooms' points
 };
 
-}  // namespace
-
-bool frontend_fits(size_t fdim, size_t ldim) { return 3 + fdim + ldim <= 7; }
-
-// All clouds of a batch in the same launches; prm: the caller's per-cloud GsParams (status / voxel count as the sort-based path leaves them).
-// centres (host [nr, 3]) / num_points: reduce only the buckets the num_points rows nearest to every room's centre can lie in (the staged reduction above);
-// the outputs then hold those buckets' rows, in key order, and d_om their count.  centres NULL: every bucket.
-int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const int32_t* d_c, size_t ldim, const int64_t* room_off, size_t nr, float dl,
-                          float* d_op, float* d_of, int32_t* d_oc, int64_t* d_om, GsParams* prm, hipStream_t s, const float* centres, size_t num_points) {
-    FeState& S = per_stream<FeState>(s);
-    S.tile_clouds = 0;
-    FeTab t; t.nr = (int)nr;
+// the room table of a call, as every kernel takes it
+int fe_room_table(const int64_t* room_off, size_t nr, FeTab& t) {
+    t.nr = (int)nr;
     int maxn = 0;
     for (size_t r = 0; r < nr; ++r) {
         const long n = (long)(room_off[r + 1] - room_off[r]);
@@ -998,6 +1002,87 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
     t.off[nr] = (int)room_off[nr];
     t.n_total = (int)room_off[nr];
     t.chunks_max = (maxn + FE_CH - 1) / FE_CH;
+    t.ovf_cap = 0;
+    return SSDR_OK;
+}
+
+// what depends on the rooms' points and dl alone (none of it on a centre): bounding box, grid and bucket geometry, the [chunk][bucket] counts and their scans, one
+// work item per non-empty bucket; prm: every room's status and grid parameters; counters: zeroed as a call starts them, [0] = the items
+struct FeTables { float* partial; FeGeom* geom; unsigned* cntm; unsigned* tot; unsigned* boff; FeItem* items; };
+void fe_launch_tables(const FeTab& t, const float* d_p, float dl, GsParams* prm, const FeTables& T, int* counters, hipStream_t s) {
+    const unsigned R = (unsigned)t.nr;
+    hipLaunchKernelGGL(fe_minmax_partial, dim3(PB, R), dim3(BS), 0, s, t, d_p, T.partial);
+    hipLaunchKernelGGL(fe_params, dim3(R), dim3(BS), 0, s, t, T.partial, dl, prm, T.geom, counters);
+    hipLaunchKernelGGL(fe_count, dim3(t.chunks_max, R), dim3(FE_NT), 0, s, t, d_p, T.geom, prm, T.cntm);
+    hipLaunchKernelGGL(fe_colscan, dim3(FE_NBMAX / BS, R), dim3(BS), 0, s, t, T.geom, T.cntm, T.tot);
+    hipLaunchKernelGGL(fe_bscan, dim3(R), dim3(FE_NT), 0, s, t, T.geom, T.tot, T.boff, T.items, counters);
+}
+
+}  // namespace
+
+// A room plan: the tables of fe_launch_tables in buffers of its own (not the per-stream scratch: calls on any stream read them, a call without a plan on the same
+// stream does not touch them), and the identity of what they were built from.  Read-only once built.
+struct FePlan {
+    DevBuf partial, geom, cntm, tot, boff, items, counters, prm;
+    const float* d_p = nullptr; const float* d_f = nullptr; const int32_t* d_c = nullptr; size_t fdim = 0, ldim = 0, nr = 0; float dl = 0.f;
+    std::vector<int64_t> room_off; FeTab t;
+    hipStream_t stream = nullptr; hipEvent_t built = nullptr;          // the stream the tables were built on; recorded behind the last of their launches
+    mutable std::mutex mu; mutable std::vector<hipStream_t> waited;      // the other streams that have waited for `built`
+    FeTables tables() const { FeTables T; T.partial = partial.as<float>(); T.geom = geom.as<FeGeom>(); T.cntm = cntm.as<unsigned>(); T.tot = tot.as<unsigned>();
+                              T.boff = boff.as<unsigned>(); T.items = items.as<FeItem>(); return T; }
+    ~FePlan() { if (built) (void)hipEventDestroy(built); }
+};
+
+bool frontend_fits(size_t fdim, size_t ldim) { return 3 + fdim + ldim <= 7; }
+
+// the five launches of fe_launch_tables into a new plan's buffers, on `s`; the event lets a call on another stream wait for them
+int frontend_plan_build(const float* d_p, const float* d_f, size_t fdim, const int32_t* d_c, size_t ldim, const int64_t* room_off, size_t nr, float dl, hipStream_t s,
+                        FePlan** out) {
+    std::unique_ptr<FePlan> P(new FePlan);
+    SSDR_TRY(fe_room_table(room_off, nr, P->t));
+    P->d_p = d_p; P->d_f = d_f; P->d_c = d_c; P->fdim = fdim; P->ldim = ldim; P->nr = nr; P->dl = dl; P->room_off.assign(room_off, room_off + nr + 1); P->stream = s;
+    const FeTab& t = P->t;
+    SSDR_TRY(P->partial.reserve(24 * (size_t)PB * nr)); SSDR_TRY(P->geom.reserve(sizeof(FeGeom) * nr)); SSDR_TRY(P->counters.reserve(256 + 8 * RADIX_MAX_SEG));
+    SSDR_TRY(P->cntm.reserve(4 * (size_t)FE_NBMAX * t.chunks_max * nr)); SSDR_TRY(P->tot.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(P->boff.reserve(4 * (size_t)(FE_NBMAX + 1) * nr));
+    SSDR_TRY(P->items.reserve(sizeof(FeItem) * (size_t)FE_NBMAX * nr)); SSDR_TRY(P->prm.reserve(sizeof(GsParams) * nr));
+    SSDR_HIP(hipEventCreateWithFlags(&P->built, hipEventDisableTiming));
+    fe_launch_tables(t, d_p, dl, P->prm.as<GsParams>(), P->tables(), P->counters.as<int>(), s);
+    SSDR_HIP(hipGetLastError());
+    SSDR_HIP(hipEventRecord(P->built, s));
+    *out = P.release();
+    return SSDR_OK;
+}
+
+// waits for the device: a call that reads the plan may still be in flight on any stream
+int frontend_plan_destroy(FePlan* P) {
+    if (!P) return SSDR_OK;
+    const hipError_t e = hipDeviceSynchronize();
+    delete P;
+    if (e != hipSuccess) { set_error("rooms_plan_destroy: hipDeviceSynchronize failed: %s", hipGetErrorString(e)); return SSDR_ERR_HIP; }
+    return SSDR_OK;
+}
+
+// the plan answers for exactly the inputs it was built from
+int frontend_plan_check(const FePlan* P, const float* d_p, const float* d_f, size_t fdim, const int32_t* d_c, size_t ldim, const int64_t* room_off, size_t nr, float dl) {
+    const char* what = nullptr;
+    if (P->d_p != d_p || P->d_f != d_f || P->d_c != d_c) what = "input pointers";
+    else if (P->fdim != fdim || P->ldim != ldim) what = "fdim / ldim";
+    else if (P->nr != nr) what = "num_clouds";
+    else if (!std::equal(room_off, room_off + nr + 1, P->room_off.begin())) what = "cloud_offsets";
+    else if (!(P->dl == dl)) what = "sampleDl";
+    if (what) { set_error("tile_from_rooms_planned_batch: the plan was built from other %s (rebuild it: ssdr_rooms_plan_create_dev)", what); return SSDR_ERR_INVALID; }
+    return SSDR_OK;
+}
+
+// All clouds of a batch in the same launches; prm: the caller's per-cloud GsParams (status / voxel count as the sort-based path leaves them).
+// centres (host [nr, 3]) / num_points: reduce only the buckets the num_points rows nearest to every room's centre can lie in (the staged reduction above);
+// the outputs then hold those buckets' rows, in key order, and d_om their count.  centres NULL: every bucket.
+int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const int32_t* d_c, size_t ldim, const int64_t* room_off, size_t nr, float dl,
+                          float* d_op, float* d_of, int32_t* d_oc, int64_t* d_om, GsParams* prm, hipStream_t s, const float* centres, size_t num_points, const FePlan* plan) {
+    FeState& S = per_stream<FeState>(s);
+    S.tile_clouds = 0;
+    FeTab t;
+    SSDR_TRY(fe_room_table(room_off, nr, t));
     // The reduction reads a bucket's records in place (no LDS image: 19 KB instead of 51 KB per workgroup, four workgroups per CU by registers) and every
     // bucket's rows go to the overflow region, which then holds up to one row per point.  Measured on one box (tools/gpu_fe_ab.sh, round 5): fe_reduce 0.51-0.56
     // -> 0.45-0.46 ms, front end 1.23-1.26 -> 1.16-1.18 ms, headline 178.2-178.7 -> 180.9-181.8 Mpoints/s; 5 / 6 waves per SIMD (spilling 24 / 36 dwords)
@@ -1007,9 +1092,13 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
     static const int fe_pad = [] { const char* e = getenv("SSDR_FE_PADLDS"); return e ? atoi(e) : 0; }();      // (development: unused dynamic LDS caps the workgroups per CU)
     t.ovf_cap = fe_image ? std::max(65536, t.n_total / 8) : t.n_total;
     const unsigned R = (unsigned)nr;
-    SSDR_TRY(S.partial.reserve(24 * (size_t)PB * nr)); SSDR_TRY(S.geom.reserve(sizeof(FeGeom) * nr)); SSDR_TRY(S.counters.reserve(256 + 8 * RADIX_MAX_SEG));
-    SSDR_TRY(S.cntm.reserve(4 * (size_t)FE_NBMAX * t.chunks_max * nr)); SSDR_TRY(S.tot.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.boff.reserve(4 * (size_t)(FE_NBMAX + 1) * nr));
-    SSDR_TRY(S.items.reserve(sizeof(FeItem) * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.nocc.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.trow.reserve(4 * (size_t)FE_NBMAX * nr));
+    SSDR_TRY(S.counters.reserve(256 + 8 * RADIX_MAX_SEG));
+    if (!plan) {
+        SSDR_TRY(S.partial.reserve(24 * (size_t)PB * nr)); SSDR_TRY(S.geom.reserve(sizeof(FeGeom) * nr));
+        SSDR_TRY(S.cntm.reserve(4 * (size_t)FE_NBMAX * t.chunks_max * nr)); SSDR_TRY(S.tot.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.boff.reserve(4 * (size_t)(FE_NBMAX + 1) * nr));
+        SSDR_TRY(S.items.reserve(sizeof(FeItem) * (size_t)FE_NBMAX * nr));
+    }
+    SSDR_TRY(S.nocc.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.trow.reserve(4 * (size_t)FE_NBMAX * nr));
     SSDR_TRY(S.lrc.reserve((size_t)FE_NBMAX * FE_LR * nr)); SSDR_TRY(S.pre.reserve(2 * (size_t)FE_NBMAX * FE_LR * nr));
     SSDR_TRY(S.rowcnt.reserve(4 * (size_t)FE_ROWCAP * nr));
     SSDR_TRY(S.rec.reserve(32 * ((size_t)t.n_total + t.ovf_cap) + 64));
@@ -1018,7 +1107,12 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
         hipLaunchKernelGGL(fe_rcp_init, dim3((FE_CAP + 256) / 256), dim3(256), 0, s, S.rcp.as<float>());
         S.rcp_ready = true;
     }
-    FeGeom* geom = S.geom.as<FeGeom>(); int* counters = S.counters.as<int>(); FeItem* items = S.items.as<FeItem>();
+    // the centre-independent tables: this call's own (the per-stream scratch), or the plan's (read-only here; the only list the stages write is S.work)
+    FeTables own; own.partial = S.partial.as<float>(); own.geom = S.geom.as<FeGeom>(); own.cntm = S.cntm.as<unsigned>(); own.tot = S.tot.as<unsigned>();
+    own.boff = S.boff.as<unsigned>(); own.items = S.items.as<FeItem>();
+    const FeTables T = plan ? plan->tables() : own;
+    const FeGeom* geom = T.geom; int* counters = S.counters.as<int>(); const FeItem* items = T.items;
+    const unsigned* cntm = T.cntm; const unsigned* tot = T.tot; const unsigned* boff = T.boff;
     FeRedArgs ra; ra.t = t; ra.items = items; ra.prm = prm; ra.counters = counters; ra.rcp = S.rcp.as<float>(); ra.rec = S.rec.as<uint4>();
     ra.nocc = S.nocc.as<unsigned>(); ra.trow = S.trow.as<unsigned>(); ra.lrc = S.lrc.as<unsigned char>(); ra.fdim = (int)fdim; ra.ldim = (int)ldim;
     // the staged reduction (centres given).  Stage 1's buckets follow from the buckets' point counts, their boxes and the centres: all there after fe_bscan, so the
@@ -1032,7 +1126,7 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
         SSDR_TRY(S.okey.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.odmax.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.ocum.reserve(4 * (size_t)FE_NBMAX * nr));
         SSDR_TRY(S.work.reserve(sizeof(FeItem) * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.tinfo.reserve(sizeof(FeTileInfo) * RADIX_MAX_SEG));
         if (prune) SSDR_TRY(S.flag.reserve((size_t)FE_NBMAX * nr));
-        ta.t = t; ta.geom = geom; ta.tot = S.tot.as<unsigned>(); ta.boff = S.boff.as<unsigned>(); ta.nocc = ra.nocc; ta.lrc = ra.lrc;
+        ta.t = t; ta.geom = geom; ta.tot = tot; ta.boff = boff; ta.nocc = ra.nocc; ta.lrc = ra.lrc;
         ta.flag = prune ? S.flag.as<unsigned char>() : nullptr;
         for (size_t i = 0; i < 3 * nr; ++i) ta.cen.c[i] = centres[i];
         ta.okey = S.okey.as<unsigned>(); ta.odmax = S.odmax.as<float>(); ta.ocum = S.ocum.as<unsigned>(); ta.work = S.work.as<FeItem>(); ta.counters = counters;
@@ -1048,21 +1142,24 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
     // (28 B per point) goes to the scatter, the one write of the rows (28 B per voxel: the count is the device's, bench.py adds it) to the reduction
     {
     ProfScope prof("fe_bbox_count_scan", s, 0.0);
-    hipLaunchKernelGGL(fe_minmax_partial, dim3(PB, R), dim3(BS), 0, s, t, d_p, S.partial.as<float>());
-    hipLaunchKernelGGL(fe_params, dim3(R), dim3(BS), 0, s, t, S.partial.as<float>(), dl, prm, geom, counters);
-    hipLaunchKernelGGL(fe_count, dim3(t.chunks_max, R), dim3(FE_NT), 0, s, t, d_p, geom, prm, S.cntm.as<unsigned>());
-    hipLaunchKernelGGL(fe_colscan, dim3(FE_NBMAX / BS, R), dim3(BS), 0, s, t, geom, S.cntm.as<unsigned>(), S.tot.as<unsigned>());
-    hipLaunchKernelGGL(fe_bscan, dim3(R), dim3(FE_NT), 0, s, t, geom, S.tot.as<unsigned>(), S.boff.as<unsigned>(), items, counters);
+    if (plan) {
+        // the plan's launches ran on its own stream: the first call on every other stream is ordered behind them
+        if (s != plan->stream) {
+            std::lock_guard<std::mutex> lk(plan->mu);
+            if (std::find(plan->waited.begin(), plan->waited.end(), s) == plan->waited.end()) { SSDR_HIP(hipStreamWaitEvent(s, plan->built, 0)); plan->waited.push_back(s); }
+        }
+        hipLaunchKernelGGL(fe_plan_begin, dim3(R), dim3(64), 0, s, plan->prm.as<GsParams>(), plan->counters.as<int>(), prm, counters);
+    } else fe_launch_tables(t, d_p, dl, prm, own, counters, s);
     if (prune) hipLaunchKernelGGL(fe_tile_order, dim3(R), dim3(FE_NT), 0, s, ta);
     }
 #define FE_LAUNCH_SCATTER(MODE)                                                                                                                                              \
     do {                                                                                                                                                                     \
         if (fdim == 3 && ldim == 1)                                                                                                                                          \
-            hipLaunchKernelGGL((fe_scatter<3, 1, MODE>), dim3(t.chunks_max, R), dim3(FE_SNT), 0, s, t, d_p, d_f, (int)fdim, (const int*)d_c, (int)ldim, geom, S.cntm.as<unsigned>(), \
-                               S.boff.as<unsigned>(), S.rec.as<uint4>(), flag, tinfo, nscat);                                                                                \
+            hipLaunchKernelGGL((fe_scatter<3, 1, MODE>), dim3(t.chunks_max, R), dim3(FE_SNT), 0, s, t, d_p, d_f, (int)fdim, (const int*)d_c, (int)ldim, geom, cntm, \
+                               boff, S.rec.as<uint4>(), flag, tinfo, nscat);                                                                                \
         else                                                                                                                                                                 \
-            hipLaunchKernelGGL((fe_scatter<-1, -1, MODE>), dim3(t.chunks_max, R), dim3(FE_SNT), 0, s, t, d_p, d_f, (int)fdim, (const int*)d_c, (int)ldim, geom, S.cntm.as<unsigned>(), \
-                               S.boff.as<unsigned>(), S.rec.as<uint4>(), flag, tinfo, nscat);                                                                                \
+            hipLaunchKernelGGL((fe_scatter<-1, -1, MODE>), dim3(t.chunks_max, R), dim3(FE_SNT), 0, s, t, d_p, d_f, (int)fdim, (const int*)d_c, (int)ldim, geom, cntm, \
+                               boff, S.rec.as<uint4>(), flag, tinfo, nscat);                                                                                \
     } while (0)
     {
     ProfScope prof("fe_scatter", s, (double)(12 + 4 * (fdim + ldim)) * (double)t.n_total);
@@ -1105,7 +1202,7 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
     else hipLaunchKernelGGL((fe_reduce<-1, -1, true>), dim3(ctx().num_cu * (fe_wgs > 0 ? fe_wgs : 3)), dim3(FE_RNT), 0, s, ra);
     }
     ProfScope prof_move("fe_rows_move", s, 0.0);
-    hipLaunchKernelGGL(fe_rowpre, dim3(256, R), dim3(BS), 0, s, geom, S.boff.as<unsigned>(), S.lrc.as<unsigned char>(), S.pre.as<unsigned short>(), S.rowcnt.as<unsigned>());
+    hipLaunchKernelGGL(fe_rowpre, dim3(256, R), dim3(BS), 0, s, geom, boff, S.lrc.as<unsigned char>(), S.pre.as<unsigned short>(), S.rowcnt.as<unsigned>());
     hipLaunchKernelGGL(fe_rowscan, dim3(R), dim3(FE_NT), 0, s, geom, S.rowcnt.as<unsigned>(), prm, (long long*)d_om);
     FeMoveArgs ma; ma.t = t; ma.geom = geom; ma.items = items; ma.counters = counters; ma.rec = S.rec.as<uint4>(); ma.nocc = S.nocc.as<unsigned>();
     ma.trow = S.trow.as<unsigned>(); ma.lrc = S.lrc.as<unsigned char>(); ma.pre = S.pre.as<unsigned short>(); ma.rowbase = S.rowcnt.as<unsigned>(); ma.fdim = (int)fdim; ma.ldim = (int)ldim;

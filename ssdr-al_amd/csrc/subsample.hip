@@ -540,21 +540,27 @@ int prune_device(const float* d_p, size_t n, float w, const uint8_t* d_rgb, cons
 
 // frontend.hip: bucket partition + per-bucket LDS reduction (rows of at most 7 words, grids of at most 16384 buckets of 1024 voxels)
 bool frontend_fits(size_t fdim, size_t ldim);
+struct FePlan;          // a room plan: what the partition derives from the rooms' points and dl alone, kept between calls (frontend.hip)
 int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const int32_t* d_c, size_t ldim, const int64_t* room_off, size_t nr, float dl,
-                          float* d_op, float* d_of, int32_t* d_oc, int64_t* d_om, GsParams* prm, hipStream_t s, const float* centres, size_t num_points);
+                          float* d_op, float* d_of, int32_t* d_oc, int64_t* d_om, GsParams* prm, hipStream_t s, const float* centres, size_t num_points, const FePlan* plan);
+int frontend_plan_build(const float* d_p, const float* d_f, size_t fdim, const int32_t* d_c, size_t ldim, const int64_t* room_off, size_t nr, float dl, hipStream_t s,
+                        FePlan** out);
+int frontend_plan_destroy(FePlan* plan);
+int frontend_plan_check(const FePlan* plan, const float* d_p, const float* d_f, size_t fdim, const int32_t* d_c, size_t ldim, const int64_t* room_off, size_t nr, float dl);
 int frontend_tile_stats(hipStream_t s, int32_t* stage, int32_t* reduced, int32_t* buckets, size_t nr);
 void frontend_tile_forget(hipStream_t s);
 int frontend_scatter_stats(hipStream_t s, int64_t* scattered, int64_t* points, size_t nr);
 
 // centres (host [nr, 3]) / num_points: the partition path may leave out the buckets that cannot hold one of the num_points rows nearest to a room's centre
-// (ssdr_tile_from_rooms_batch_dev); NULL: every row of every cloud
+// (ssdr_tile_from_rooms_batch_dev); NULL: every row of every cloud.  plan (optional): the partition path reads its tables instead of deriving them; the sort has no use for it
 int grid_subsample_batch_device(const float* d_p, const float* d_f, size_t fdim, const int32_t* d_c, size_t ldim, const int64_t* room_off, size_t nr, float dl,
-                                float* d_op, float* d_of, int32_t* d_oc, int64_t* d_om, hipStream_t s, int method, const float* centres = nullptr, size_t num_points = 0) {
+                                float* d_op, float* d_of, int32_t* d_oc, int64_t* d_om, hipStream_t s, int method, const float* centres = nullptr, size_t num_points = 0,
+                                const FePlan* plan = nullptr) {
     GsState& S = gs(s);
     if (method != SSDR_SUBSAMPLE_SORT && frontend_fits(fdim, ldim)) {
         S.last_clouds = (int)nr;
         SSDR_TRY(S.params.reserve(sizeof(GsParams) * nr));
-        return frontend_batch_device(d_p, d_f, fdim, d_c, ldim, room_off, nr, dl, d_op, d_of, d_oc, d_om, S.params.as<GsParams>(), s, centres, num_points);
+        return frontend_batch_device(d_p, d_f, fdim, d_c, ldim, room_off, nr, dl, d_op, d_of, d_oc, d_om, S.params.as<GsParams>(), s, centres, num_points, plan);
     }
     if (centres) frontend_tile_forget(s);          // (not staged: the stats of an earlier call on this stream no longer apply)
     CloudTab t; t.nr = (int)nr;
@@ -647,11 +653,11 @@ int ssdr_grid_subsample_batch_dev(const float* d_points, const float* d_features
  * features, d_labels = the sub-sampled classes), with the same tiles bit for bit — but d_sub_* receive only the rows of the spatial buckets that can hold one
  * of the num_points rows nearest to a cloud's centre (ascending voxel key), d_sub_m their count, and d_out_idx counts among those rows.  Stateless: which
  * buckets are reduced follows from this call's inputs alone.  Under SSDR_SUBSAMPLE_SORT (or rows of more than 7 words) every row is produced. */
-int ssdr_tile_from_rooms_batch_dev(const float* d_points, const float* d_features, size_t fdim, const int32_t* d_classes, size_t ldim,
-                                   const int64_t* cloud_offsets, size_t num_clouds, float sampleDl,
-                                   float* d_sub_points, float* d_sub_features, int32_t* d_sub_classes, int64_t* d_sub_m,
-                                   const float* centers, size_t num_points, const int32_t* d_perm, const float* d_dup_u, float color_scale,
-                                   float* d_out_xyz, float* d_out_feat, int32_t* d_out_idx, int32_t* d_out_labels, void* stream) {
+static int tile_from_rooms(const FePlan* plan, const float* d_points, const float* d_features, size_t fdim, const int32_t* d_classes, size_t ldim,
+                           const int64_t* cloud_offsets, size_t num_clouds, float sampleDl,
+                           float* d_sub_points, float* d_sub_features, int32_t* d_sub_classes, int64_t* d_sub_m,
+                           const float* centers, size_t num_points, const int32_t* d_perm, const float* d_dup_u, float color_scale,
+                           float* d_out_xyz, float* d_out_feat, int32_t* d_out_idx, int32_t* d_out_labels, void* stream) {
     if (!d_points || !d_sub_points || !cloud_offsets || !d_sub_m || num_clouds == 0 || num_clouds > RADIX_MAX_SEG) { set_error("tile_from_rooms_batch: bad arguments (1..%d clouds)", RADIX_MAX_SEG); return SSDR_ERR_INVALID; }
     if (!(sampleDl > 0.f)) { set_error("tile_from_rooms_batch: sampleDl must be > 0"); return SSDR_ERR_INVALID; }
     if (d_features && (!fdim || !d_sub_features)) { set_error("tile_from_rooms_batch: features given without fdim / output"); return SSDR_ERR_INVALID; }
@@ -659,10 +665,57 @@ int ssdr_tile_from_rooms_batch_dev(const float* d_points, const float* d_feature
     if (!centers || !d_perm || !d_dup_u || !d_out_xyz || num_points == 0) { set_error("tile_from_rooms_batch: bad tile arguments"); return SSDR_ERR_INVALID; }
     if (d_out_labels && (!d_classes || ldim != 1)) { set_error("tile_from_rooms_batch: tile labels need one class column"); return SSDR_ERR_INVALID; }
     SSDR_TRY(ensure_init());
+    if (plan) SSDR_TRY(frontend_plan_check(plan, d_points, d_features, d_features ? fdim : 0, d_classes, d_classes ? ldim : 0, cloud_offsets, num_clouds, sampleDl));
     SSDR_TRY(grid_subsample_batch_device(d_points, d_features, d_features ? fdim : 0, d_classes, d_classes ? ldim : 0, cloud_offsets, num_clouds, sampleDl,
-                                         d_sub_points, d_sub_features, d_sub_classes, d_sub_m, pick_stream(stream), g_batch_method.load(), centers, num_points));
+                                         d_sub_points, d_sub_features, d_sub_classes, d_sub_m, pick_stream(stream), g_batch_method.load(), centers, num_points, plan));
     return ssdr_tile_select_batch_dev(d_sub_points, d_features ? d_sub_features : nullptr, d_features ? (int)fdim : 0, d_sub_m, cloud_offsets, num_clouds, centers, num_points,
                                       d_perm, d_dup_u, color_scale, d_out_xyz, d_out_feat, d_out_idx, d_out_labels ? d_sub_classes : nullptr, d_out_labels, stream);
+}
+
+int ssdr_tile_from_rooms_batch_dev(const float* d_points, const float* d_features, size_t fdim, const int32_t* d_classes, size_t ldim,
+                                   const int64_t* cloud_offsets, size_t num_clouds, float sampleDl,
+                                   float* d_sub_points, float* d_sub_features, int32_t* d_sub_classes, int64_t* d_sub_m,
+                                   const float* centers, size_t num_points, const int32_t* d_perm, const float* d_dup_u, float color_scale,
+                                   float* d_out_xyz, float* d_out_feat, int32_t* d_out_idx, int32_t* d_out_labels, void* stream) {
+    return tile_from_rooms(nullptr, d_points, d_features, fdim, d_classes, ldim, cloud_offsets, num_clouds, sampleDl, d_sub_points, d_sub_features, d_sub_classes, d_sub_m,
+                           centers, num_points, d_perm, d_dup_u, color_scale, d_out_xyz, d_out_feat, d_out_idx, d_out_labels, stream);
+}
+
+/* A room plan (include/ssdr_al.h): the centre-independent tables of the partition path for one uploaded set of rooms, built once on `stream`; every
+ * ssdr_tile_from_rooms_planned_batch_dev over the same rooms then starts at the bucket order.  Rows of more than 7 words take the sort, which has no tables to keep. */
+int ssdr_rooms_plan_create_dev(const float* d_points, const float* d_features, size_t fdim, const int32_t* d_classes, size_t ldim,
+                               const int64_t* cloud_offsets, size_t num_clouds, float sampleDl, void* stream, void** out_plan) {
+    if (out_plan) *out_plan = nullptr;
+    if (!d_points || !cloud_offsets || !out_plan || num_clouds == 0 || num_clouds > RADIX_MAX_SEG) { set_error("rooms_plan_create: bad arguments (1..%d clouds)", RADIX_MAX_SEG); return SSDR_ERR_INVALID; }
+    if (!(sampleDl > 0.f)) { set_error("rooms_plan_create: sampleDl must be > 0"); return SSDR_ERR_INVALID; }
+    if ((d_features && !fdim) || (d_classes && !ldim)) { set_error("rooms_plan_create: features / classes given without fdim / ldim"); return SSDR_ERR_INVALID; }
+    if (!d_features) fdim = 0;
+    if (!d_classes) ldim = 0;
+    if (!frontend_fits(fdim, ldim)) { set_error("rooms_plan_create: rows of more than 7 words take the sort, which keeps no plan"); return SSDR_ERR_UNSUPPORTED; }
+    SSDR_TRY(ensure_init());
+    FePlan* plan = nullptr;
+    SSDR_TRY(frontend_plan_build(d_points, d_features, fdim, d_classes, ldim, cloud_offsets, num_clouds, sampleDl, pick_stream(stream), &plan));
+    *out_plan = plan;
+    return SSDR_OK;
+}
+
+/* waits for the device (a call that reads the plan may be in flight on any stream), then frees the plan's buffers; NULL is accepted */
+int ssdr_rooms_plan_destroy(void* plan) {
+    if (!plan) return SSDR_OK;
+    SSDR_TRY(ensure_init());
+    return frontend_plan_destroy(static_cast<FePlan*>(plan));
+}
+
+/* ssdr_tile_from_rooms_batch_dev over the rooms `plan` was built from: the same outputs, status and stats bit for bit.  Under SSDR_SUBSAMPLE_SORT the plan is
+ * checked and then not used. */
+int ssdr_tile_from_rooms_planned_batch_dev(const void* plan, const float* d_points, const float* d_features, size_t fdim, const int32_t* d_classes, size_t ldim,
+                                           const int64_t* cloud_offsets, size_t num_clouds, float sampleDl,
+                                           float* d_sub_points, float* d_sub_features, int32_t* d_sub_classes, int64_t* d_sub_m,
+                                           const float* centers, size_t num_points, const int32_t* d_perm, const float* d_dup_u, float color_scale,
+                                           float* d_out_xyz, float* d_out_feat, int32_t* d_out_idx, int32_t* d_out_labels, void* stream) {
+    if (!plan) { set_error("tile_from_rooms_planned_batch: no plan"); return SSDR_ERR_INVALID; }
+    return tile_from_rooms(static_cast<const FePlan*>(plan), d_points, d_features, fdim, d_classes, ldim, cloud_offsets, num_clouds, sampleDl, d_sub_points, d_sub_features,
+                           d_sub_classes, d_sub_m, centers, num_points, d_perm, d_dup_u, color_scale, d_out_xyz, d_out_feat, d_out_idx, d_out_labels, stream);
 }
 
 /* What the last ssdr_tile_from_rooms_batch_dev on `stream` reduced (waits for it), per cloud (int32 [num_clouds] each, may be NULL): the stage its reduction

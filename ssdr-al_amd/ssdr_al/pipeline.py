@@ -173,6 +173,23 @@ class HotPath:
         self.timing = None
         self.pt_off = None          # where every cloud's points start in the concatenated arrays (LabelResult.to_host per cloud)
         self.pseudo_mask = self.pseudo_label = None      # the two rows of pseudo_gt over all points, resident across rounds (label_selected)
+        self._room_plan = self._room_plan_lib = None      # the loaded rooms' plan (ssdr_rooms_plan_create_dev) and the library that owns it
+
+    def _drop_room_plan(self):
+        plan, L = self._room_plan, self._room_plan_lib
+        self._room_plan = self._room_plan_lib = None
+        if plan is not None:
+            _lib.check(L.ssdr_rooms_plan_destroy(plan))
+
+    def close(self):
+        """frees what the library keeps for this object beyond its arrays: the loaded rooms' plan (waits for the device)"""
+        self._drop_room_plan()
+
+    def __del__(self):
+        try:
+            self._drop_room_plan()
+        except Exception:
+            pass
 
     # ---- setup (untimed): upload raw rooms, fix the per-room randomness, derive superpoints -------------------
     def draw_room(self, xyz, rid):
@@ -191,6 +208,7 @@ class HotPath:
         cfg = self.cfg
         N = cfg.num_points
         self.B = len(rooms)
+        self._drop_room_plan()      # the previous rooms' plan, before their arrays go
         self._dist = None           # the sharded run's static tables (labelled mask, sizes, exchange buffers) belong to the loaded rooms
         self.room_ids = list(range(len(rooms))) if room_ids is None else list(room_ids)
         self.rooms = []
@@ -224,12 +242,21 @@ class HotPath:
         # implementation of the batched grid subsample these rooms get: the bucket partition reports a cloud it cannot take (a grid of
         # more than 16384 buckets, a voxel of more than 1024 points) through its status, and the rooms then go through the sort
         self.subsample_method = 1 if os.environ.get("SSDR_SUBSAMPLE_METHOD") == "sort" else 0          # (development: A/B of the two implementations)
+        # the rooms stay as uploaded while tiles are drawn from them: what the bucket partition derives from the points alone (bounding boxes, grids, per-bucket
+        # counts and offsets) is built once, behind the upload, and every _front_end starts at the bucket order.  SSDR_FE_ROOM_PLAN=0 (development: A/B runs in
+        # one build) keeps the call that derives it every time
+        if self.subsample_method == 0 and os.environ.get("SSDR_FE_TILE_PRUNE", "1") != "0" and os.environ.get("SSDR_FE_ROOM_PLAN", "1") != "0":
+            plan = C.c_void_p()
+            _lib.check(_lib.lib().ssdr_rooms_plan_create_dev(self.raw_p.ptr, self.raw_c.ptr, 3, self.raw_l.ptr, 1, _lib.ptr(self.room_off), self.B, cfg.sub_grid_size,
+                                                             self.front_stream, C.byref(plan)))
+            self._room_plan, self._room_plan_lib = plan.value, _lib.lib()
         self._front_end()
         _lib.sync()
         st = C.c_int32()
         rc = _lib.lib().ssdr_grid_subsample_status(self.front_stream, C.byref(st))
         if rc != 0 and (st.value & 6):
             self.subsample_method = 1
+            self._drop_room_plan()          # (the sort has no use for it)
             self._front_end()
             _lib.sync()
             _lib.check(_lib.lib().ssdr_grid_subsample_status(self.front_stream, None))
@@ -385,6 +412,11 @@ class HotPath:
         # the bucket partition reduces only the buckets the tiles' rows can lie in (sub_* / sub_m then hold those rows); SSDR_FE_TILE_PRUNE=0 (development:
         # A/B runs) and the sort keep the two calls
         if self.subsample_method == 0 and os.environ.get("SSDR_FE_TILE_PRUNE", "1") != "0":
+            if self._room_plan is not None and os.environ.get("SSDR_FE_ROOM_PLAN", "1") != "0":
+                _lib.check(L.ssdr_tile_from_rooms_planned_batch_dev(self._room_plan, self.raw_p.ptr, self.raw_c.ptr, 3, self.raw_l.ptr, 1, _lib.ptr(self.room_off), self.B,
+                                                                    cfg.sub_grid_size, self.sub_p.ptr, self.sub_c.ptr, self.sub_l.ptr, self.sub_m.ptr, _lib.ptr(self.centers),
+                                                                    cfg.num_points, self.perm.ptr, self.dup.ptr, 1.0 / 255.0, self.xyz.ptr, self.feat.ptr, None, self.tile_l.ptr, st))
+                return
             _lib.check(L.ssdr_tile_from_rooms_batch_dev(self.raw_p.ptr, self.raw_c.ptr, 3, self.raw_l.ptr, 1, _lib.ptr(self.room_off), self.B, cfg.sub_grid_size,
                                                         self.sub_p.ptr, self.sub_c.ptr, self.sub_l.ptr, self.sub_m.ptr, _lib.ptr(self.centers), cfg.num_points,
                                                         self.perm.ptr, self.dup.ptr, 1.0 / 255.0, self.xyz.ptr, self.feat.ptr, None, self.tile_l.ptr, st))
