@@ -94,6 +94,13 @@ int ssdr_knn_status(void* stream, int32_t* out4);
  * kernels); this folds the tickets of the calls that HAVE finished and returns SSDR_ERR_INTERNAL if one of them overflowed.  For
  * callers that keep several batches in flight on `stream` and must not wait for the newest one (ssdr_al/pipeline.py). */
 int ssdr_knn_status_poll(void* stream, int32_t* out4);
+/* Read-only view of what the newest KNN call on `stream` counted on the device (waits for the stream; folds and clears nothing, so
+ * ssdr_knn_status / _poll report afterwards as if it had not been called).  out16 (host): [0], [1] rows handed to the tree walk (K = 16, K = 1),
+ * [2] grid status bits, [3] rows that left the grid unsettled, [4], [5] rows of the second pass, [6] balls, [7] unused, [8], [9] rows answered
+ * again on complete trees, [10..12] the forest's words (-, status, deepest tree), [13..15] zero.  After a call without a grid [0..9] are zero.
+ * desc_out (optional, host float[12]): n, c, nx, ny, nz, lo[3], hi[3], slack of support set `set` of that call's grid, as the device
+ * computed them; left untouched when the call had no such set.  The integers n, nx, ny, nz travel as float: exact up to 2^24, rounded above. */
+int ssdr_knn_counters(void* stream, int32_t* out16, size_t set, float* desc_out);
 
 /* ---- KNN pyramid (replaces the loop of tf_map, S3/s3dis_dataset.py:156-183) ------------------
  * For level i in [0,num_layers): N_0 = npts, N_{i+1} = N_i / ratio[i] (integer division);

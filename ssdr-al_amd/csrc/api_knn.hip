@@ -228,6 +228,27 @@ int ssdr_knn_status_poll(void* stream, int32_t* out4) {
     return SSDR_OK;
 }
 
+int ssdr_knn_counters(void* stream, int32_t* out16, size_t set, float* desc_out) {
+    if (!out16) { set_error("knn_counters: NULL output"); return SSDR_ERR_INVALID; }
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream);
+    KnnState& S = st(s);
+    SSDR_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < TICKET_WORDS; ++i) out16[i] = 0;
+    // the direct read of ssdr_knn_status, without its folding: tickets, folded words and device counters stay as they are
+    if (S.grid.need.p && S.grid.nsets > 0) {
+        SSDR_HIP(hipMemcpy(out16, S.grid.counters(), 4 * 10, hipMemcpyDeviceToHost));
+        if (desc_out && set < (size_t)S.grid.nsets) {
+            GridDesc d;
+            SSDR_HIP(hipMemcpy(&d, S.grid.desc.as<GridDesc>() + set, sizeof(GridDesc), hipMemcpyDeviceToHost));
+            const float v[12] = {(float)d.n, d.c, (float)d.nx, (float)d.ny, (float)d.nz, d.lo[0], d.lo[1], d.lo[2], d.hi[0], d.hi[1], d.hi[2], d.slack};
+            for (int i = 0; i < 12; ++i) desc_out[i] = v[i];
+        }
+    }
+    if (S.forest.counters.p) SSDR_HIP(hipMemcpy(out16 + 10, S.forest.counters.p, 4 * 3, hipMemcpyDeviceToHost));
+    return SSDR_OK;
+}
+
 int ssdr_knn_batch_distance_pick(const float* batch_data, size_t batch_size, size_t npts, size_t dim, float* batch_queries, size_t nqueries,
                                  size_t K, int64_t* batch_indices, uint32_t seed) {
     if (dim != 3) { set_error("dim=%zu: only dim == 3 is implemented", dim); return SSDR_ERR_UNSUPPORTED; }

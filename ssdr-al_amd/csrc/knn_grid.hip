@@ -10,7 +10,7 @@
 //              cell order, scans the 3 x 3 rows of cells around its own cell (x is the fastest cell dimension: each row is one
 //              contiguous range), keeps the K + 1 best in registers, and accepts when the (K+1)-th distance lies inside the
 //              radius the scanned block guarantees; otherwise the block grows (5^3, 7^3).
-//   hand-over  a row with two equal distances among its K + 1 best, with the K-th and (K+1)-th closer than 2^-19 relative
+//   hand-over  a row with two equal distances among its K + 1 best, with the K-th and (K+1)-th closer than 2^-17 relative
 //              (a tree bound rounded the other way could have pruned one of them), with fewer than K + 1 support points, or
 //              not settled inside the 7^3 block goes to a work list and is answered by kd_walk on the exact nanoflann
 //              tree (kdtree.hip); only support sets that own such rows get their tree built (device-side flags).
@@ -104,7 +104,9 @@ __global__ __launch_bounds__(PREP_NT) void grid_prepare_kernel(GridDesc* desc, i
         }
         d.c = c; d.inv_c = 1.0f / c;
         d.nx = (int)floorf(ex / c) + 1; d.ny = (int)floorf(ey / c) + 1; d.nz = (int)floorf(ez / c) + 1;
-        if ((long long)d.nx * d.ny * d.nz > d.cell_cap) { d.nx = d.ny = d.nz = 1; d.c = emax * 2.f + 1.f; d.inv_c = 1.0f / d.c; }      // unreachable safety net
+        // reached by clouds of exact copies spread far apart (100 places x 30 copies over 1000 m): the copies put d^2 = 0 into the first bin, the measured
+        // radius is ~1e-6, and 64 growth steps of 1.26 (2.6e6 x) do not bring the table under its cap.  One cell: every row goes through the retry pass.
+        if ((long long)d.nx * d.ny * d.nz > d.cell_cap) { d.nx = d.ny = d.nz = 1; d.c = emax * 2.f + 1.f; d.inv_c = 1.0f / d.c; }
         d.ncell = d.nx * d.ny * d.nz;
         for (int k = 0; k < 3; ++k) { d.lo[k] = mn[k]; d.hi[k] = mx[k]; }
         if (n == 0) { d.nx = d.ny = d.nz = 1; d.ncell = 1; d.lo[0] = d.lo[1] = d.lo[2] = 0.f; d.c = 1.f; d.inv_c = 1.f; }

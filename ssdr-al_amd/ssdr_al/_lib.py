@@ -160,6 +160,7 @@ def lib():
         L.ssdr_memcpy_h2d_on.argtypes = [vp, vp, sz, vp]
         L.ssdr_memcpy_d2h_on.argtypes = [vp, vp, sz, vp]
         L.ssdr_knn_status_poll.argtypes = [vp, vp]
+        L.ssdr_knn_counters.argtypes = [vp, vp, sz, vp]
         L.ssdr_grid_subsample_status.argtypes = [vp, vp]
         L.ssdr_grid_subsample_set_method.argtypes = [i32]
         L.ssdr_randla_infer_rows_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -83,3 +83,22 @@ def knn_status(stream=None, wait=True):
     L = _lib.lib()
     _lib.check(L.ssdr_knn_status(stream, out) if wait else L.ssdr_knn_status_poll(stream, out))
     return tuple(out)
+
+
+def knn_counters(stream=None, set=None):
+    """Waits for `stream` and returns the device counters of the newest KNN call on it (ssdr_knn_counters; reads only, so knn_status
+    reports afterwards as before): an int32 array of 16 words — [0], [1] rows handed to the tree walk (K = 16, K = 1), [2] grid status
+    bits, [3] unsettled rows, [4], [5] rows of the second pass, [6] balls, [8], [9] rows answered again on complete trees, [10..12] the
+    forest's words; [0..9] are zero after a call without a grid.  With `set` the pair (counters, desc): desc is the grid descriptor of that
+    support set as the device computed it (n, nx, ny, nz ints; c, slack float32; lo, hi float32[3]), or None if the call had no such set.
+    The C ABI carries the descriptor as floats, so n, nx, ny, nz are exact only up to 2^24 (a set of more points reports n rounded)."""
+    out = np.zeros(16, np.int32)
+    if set is None:
+        _lib.check(_lib.lib().ssdr_knn_counters(stream, _lib.ptr(out), 0, None))
+        return out
+    d = np.full(12, np.nan, np.float32)
+    _lib.check(_lib.lib().ssdr_knn_counters(stream, _lib.ptr(out), int(set), _lib.ptr(d)))
+    if np.isnan(d[0]):
+        return out, None
+    return out, {"n": int(d[0]), "c": d[1], "nx": int(d[2]), "ny": int(d[3]), "nz": int(d[4]), "lo": d[5:8].copy(), "hi": d[8:11].copy(),
+                 "slack": d[11]}

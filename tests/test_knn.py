@@ -182,11 +182,12 @@ def test_tree_hand_over_cut_to_balls(backend, orc, scale, monkeypatch, capfd):
 
 
 @pytest.mark.gpu
-def test_complete_rebuild_of_several_large_trees_in_one_launch(monkeypatch, capfd):
+def test_complete_rebuild_of_several_large_trees_in_one_launch(monkeypatch):
     """The re-build behind the hand-over (complete trees for rows the ball-cut trees could not settle) takes one workgroup per flagged tree up to 4096 points
     and kd_levels_kernel — W co-operating workgroups, a meeting point per level — above: a 40 960-point tree took its one workgroup 6.6 ms.  Balls far too
     small (SSDR_KNN_BALL_SCALE=1e-9) send every handed-over row of a four-tile pyramid there: several large trees at once, levels 0 and 1 through the new
-    kernel, the deeper ones through the old one; the pyramid must be the default path's, bit for bit, and SSDR_KD_LEVELS=0 (the old kernel alone) as well."""
+    kernel, the deeper ones through the old one; the pyramid must be the default path's, bit for bit.  (SSDR_KD_LEVELS=0, the old kernel alone, is static and
+    read once per process: test_knn_paths.py::test_rebuild_levels_switch runs it in a process of its own.)"""
     from conftest import GPU_LIB, _have_gpu
     if not _have_gpu():
         pytest.skip("no GPU")
@@ -201,13 +202,10 @@ def test_complete_rebuild_of_several_large_trees_in_one_launch(monkeypatch, capf
             xyz[b] = xyz[b][rng.permutation(N)]
         ref = knn.knn_pyramid(xyz, [4, 4, 4, 4, 2], 16)
         monkeypatch.setenv("SSDR_KNN_BALL_SCALE", "1e-9")
-        monkeypatch.setenv("SSDR_KNN_DEBUG", "1")
-        capfd.readouterr()
         got = knn.knn_pyramid(xyz, [4, 4, 4, 4, 2], 16)
-        assert knn.knn_status()[0] > 0                     # rows were handed over (the status call prints the debug line)
-        err = capfd.readouterr().err
-        line = [ln for ln in err.splitlines() if "again on complete trees" in ln][-1]
-        assert int(line.split(";")[-1].split()[0]) > 20, line      # the K = 16 rows that went through the complete trees
+        c = knn.knn_counters()
+        assert knn.knn_status()[0] == c[0] > 0             # rows were handed over
+        assert c[8] > 20, list(c)                          # the K = 16 rows that went through the complete trees
         for a, b in zip(ref, got):
             for x, y in zip(a, b):
                 assert np.array_equal(x, y)
