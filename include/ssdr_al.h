@@ -216,7 +216,9 @@ int ssdr_tile_from_rooms_stats(void* stream, int32_t* out_stage, int32_t* out_re
 /* Per cloud of the last ssdr_tile_from_rooms_batch_dev on `stream` (waits for it; int64 [num_clouds] each, may be NULL): the 32-byte records its partition wrote
  * and the cloud's points.  The partition writes only the records of the buckets a stage reduces: records < points for a cloud whose first stage sufficed with a
  * part of its buckets, records == points for a cloud that went on to a later stage or was reduced whole.  -1 / -1 when the call took the sort; records -1 under
- * SSDR_FE_SCATTER_PRUNE=0 (development: the one scatter of every record, which does not count). */
+ * SSDR_FE_SCATTER_PRUNE=0 (development: the one scatter of every record, which does not count).  A planned call whose plan holds the records (below) writes
+ * none: for it the first number is "records the stages were given", not "records written" — the points of the buckets the first stage was handed, plus, for a
+ * cloud that went on, the points of all its other buckets — which is the number the unplanned call reports for the same inputs. */
 int ssdr_tile_from_rooms_scatter_stats(void* stream, int64_t* out_scattered, int64_t* out_points, size_t num_clouds);
 /* Room plans: a caller that uploads a set of rooms once and draws many tiles from it (every tile has its own centres) builds a plan behind the upload and
  * hands it to every call.  The plan keeps what the partition path derives from the points and sampleDl alone — every cloud's grid and bucket geometry, its status
@@ -230,14 +232,23 @@ int ssdr_tile_from_rooms_scatter_stats(void* stream, int64_t* out_scattered, int
  *                                when d_points, d_features, d_classes, fdim, ldim, cloud_offsets, num_clouds or sampleDl differ from the plan's.  Under
  *                                SSDR_SUBSAMPLE_SORT the plan is checked and not used.
  *   ssdr_rooms_plan_destroy      waits for the device, then frees the plan (NULL is accepted).
- * CONTRACT: a plan is valid while the bytes behind d_points and cloud_offsets are unchanged.  The library compares pointers and offsets, not the points: a caller
- * that rewrites the points in place destroys the plan and creates it again.  (Features and classes are not part of the plan's tables; their pointers are
- * compared so that a plan stands for one uploaded set.)  A plan is read-only once built: any number of planned calls, on any streams, may share it.
+ *   ssdr_rooms_plan_info         read-only: *out_record_bytes = the bytes of the records the plan holds (0: none), *out_sorted = 1 when they are ordered inside a
+ *                                bucket (0 in this version); either pointer may be NULL.
+ * The plan also OWNS A COPY OF THE CLOUDS' ROWS: every point as a 32-byte record (xyz, its index in the cloud, features, classes) in the spatial bucket the tables
+ * assign it to — the inputs rearranged, no sum and no vote.  A planned call with such a plan runs no partition pass and does NOT READ d_points, d_features or
+ * d_classes (their pointers are still compared); its voxel reduction reads the plan's records.  Environment, read at every ssdr_rooms_plan_create_dev:
+ * SSDR_FE_PLAN_RECORDS=0 builds a plan without records (calls then write their records per call, as without this copy); SSDR_FE_PLAN_RECORDS_MAX_MB (default
+ * 4096): a plan whose records would be larger is built without them, silently (ssdr_rooms_plan_info tells).
+ * CONTRACT: a plan is valid while the bytes behind d_points, d_features, d_classes and cloud_offsets are unchanged.  The library compares pointers and offsets, not
+ * the bytes: a caller that rewrites any of them in place destroys the plan and creates it again (with records a stale plan would go on answering for the OLD rows).
+ * A plan is read-only once built: any number of planned calls, on any streams, may share it.
  * Memory: the per-chunk counts are sized for the worst case, 16384 buckets x ceil(largest cloud / 32768) chunks x num_clouds words — about 39 MB for 16 clouds
- * of up to 1.2 M points — plus 0.7 MB per cloud of bucket tables, per plan. */
+ * of up to 1.2 M points — plus 0.7 MB per cloud of bucket tables, per plan; the records add 32 bytes per raw point (431 MB for 13.46 M points), up to the cap.  A
+ * stream that only makes planned calls with records keeps 32 bytes per raw point less of scratch (its record buffer holds the rows region alone). */
 int ssdr_rooms_plan_create_dev(const float* d_points, const float* d_features, size_t fdim, const int32_t* d_classes, size_t ldim,
                                const int64_t* cloud_offsets, size_t num_clouds, float sampleDl, void* stream, void** out_plan);
 int ssdr_rooms_plan_destroy(void* plan);
+int ssdr_rooms_plan_info(void* plan, int64_t* out_record_bytes, int32_t* out_sorted);
 int ssdr_tile_from_rooms_planned_batch_dev(const void* plan, const float* d_points, const float* d_features, size_t fdim, const int32_t* d_classes, size_t ldim,
                                            const int64_t* cloud_offsets, size_t num_clouds, float sampleDl,
                                            float* d_sub_points, float* d_sub_features, int32_t* d_sub_classes, int64_t* d_sub_m,

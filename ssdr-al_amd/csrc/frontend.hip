@@ -26,7 +26,8 @@
 // voxels, against 28 (N + M) algorithmic.  The staged reduction of ssdr_tile_from_rooms_batch_dev (below) orders a room's buckets BEFORE the scatter and writes and
 // reduces only the share p of the points that lies in stage 1's buckets: 12 N + 12 N + 28 N + 32 p N (scatter) + 32 p N + 32 p M (reduce) + (32 + 28) p M (move);
 // p = 0.42 on the bench's rooms.  A room that goes on to stage 2 pays 28 N more (a second read of its points) for the other 32 (1 - p) N of records.  A call with a room
-// plan (FePlan) starts at the order: the 12 N + 12 N of minmax and count were paid once, when the plan was built.  Clouds whose grid does not fit (more than FE_NBMAX buckets of 1024 voxels) or that
+// plan (FePlan) starts at the order: the 12 N + 12 N of minmax and count were paid once, when the plan was built — and so were the scatter's 28 N + 32 N when the plan holds the
+// rooms' records (the default): such a call moves 32 p N + 32 p M (reduce, its records read from the plan) + (32 + 28) p M (move), and a room that goes on to stage 2 pays no second read.  Clouds whose grid does not fit (more than FE_NBMAX buckets of 1024 voxels) or that
 // hold a voxel of more than FE_CAP points are flagged (ssdr_grid_subsample_status) and belong to the sort-based entry point.
 #include "ssdr_internal.hpp"
 #include "block_prims.hpp"
@@ -341,8 +342,11 @@ __global__ __launch_bounds__(FE_SNT) void fe_scatter(FeTab t, const float* __res
 // ---- reduction: one workgroup per bucket ------------------------------------------------------------------------------------
 struct FeRedArgs {
     FeTab t; const FeItem* items; GsParams* prm; int* counters; const float* rcp;
-    uint4* rec; unsigned* nocc; unsigned* trow; unsigned char* lrc; int fdim, ldim;
+    const uint4* rec; uint4* rows; uint4* wrec; unsigned* nocc; unsigned* trow; unsigned char* lrc; int fdim, ldim;
 };
+// rec: the records, read only — the call's own scatter left them in the per-stream buffer, or a room plan holds them (FePlan::rec).  rows: where the rows region
+// starts (ovf_cap rows): behind the n_total records of the per-stream buffer, or that whole buffer when the records are the plan's.  wrec: the per-stream record
+// buffer as the LDS-image variant writes it (a bucket's rows over its own records); never a plan's.
 
 // IMG: the bucket's (or slice's) records are also kept in LDS and the ordered walk reads them there — 51 KB per workgroup, three workgroups per CU.
 // !IMG: the walk reads the records where the scatter left them (the workgroup has just streamed them: L2) and the rows go to the overflow region —
@@ -538,7 +542,7 @@ __global__ __launch_bounds__(FE_RNT) SSDR_WAVES_PER_EU(IMG ? 2 : FE_RED_WAVES) v
         fe_segments(L, V);
         FE_STAMP(1);
         const int nocc = L.orank[V];
-        uint4* rows = a.rec + 2 * (size_t)it.base;           // the bucket's rows go over its own records (all of them are in LDS by now) ...
+        uint4* rows = IMG ? a.wrec + 2 * (size_t)it.base : nullptr;           // the bucket's rows go over its own records (all of them are in LDS by now) ...
         unsigned sg[FE_RPT], eg[FE_RPT];
 #pragma unroll
         for (int k = 0; k < FE_RPT; ++k) { sg[k] = 0u; eg[k] = 0u; }
@@ -588,7 +592,7 @@ __global__ __launch_bounds__(FE_RNT) SSDR_WAVES_PER_EU(IMG ? 2 : FE_RED_WAVES) v
             }
             __syncthreads();
         }
-        if ((!fast || !IMG) && !L.bad) rows = a.rec + 2 * ((size_t)a.t.n_total + L.ovf);
+        if ((!fast || !IMG) && !L.bad) rows = a.rows + 2 * (size_t)L.ovf;
         const size_t tb = (size_t)r * FE_NBMAX + b;
         if (L.bad) {           // a voxel of more than FE_CAP points (or more slices / overflow rows than there is room for): not this entry point's case
             if (tid == 0) { atomicOr(&prm->status, 4); a.nocc[tb] = 0u; a.trow[tb] = 0u; }
@@ -698,7 +702,7 @@ __global__ __launch_bounds__(FE_NT) void fe_rowscan(const FeGeom* __restrict__ g
 
 // one wave per bucket: its rows to their final places
 struct FeMoveArgs {
-    FeTab t; const FeGeom* geom; const FeItem* items; const int* counters; const uint4* rec; const unsigned* nocc; const unsigned* trow;
+    FeTab t; const FeGeom* geom; const FeItem* items; const int* counters; const uint4* rec; const uint4* rows; const unsigned* nocc; const unsigned* trow;          // rec / rows: FeRedArgs' wrec / rows
     const unsigned char* lrc; const unsigned short* pre; const unsigned* rowbase; int fdim, ldim; float* out_p; float* out_f; int* out_c;
 };
 // FD / LD >= 0: row layout known at compile time (the hot path's 3 features + 1 label: one 12-byte store each for the position and the features instead of
@@ -715,7 +719,7 @@ __global__ __launch_bounds__(BS) void fe_move(FeMoveArgs a) {
         const size_t tb = (size_t)r * FE_NBMAX + b;
         const int nocc = (int)a.nocc[tb];
         const unsigned tr = a.trow[tb];
-        const uint4* rows = a.rec + 2 * ((tr & 0x80000000u) ? (size_t)a.t.n_total + (tr & 0x7fffffffu) : (size_t)tr);
+        const uint4* rows = (tr & 0x80000000u) ? a.rows + 2 * (size_t)(tr & 0x7fffffffu) : a.rec + 2 * (size_t)tr;
         const int by = (b / g.nbx) % g.nby, bz = b / (g.nbx * g.nby);
         // occupied voxels of the bucket in front of every local row
         const unsigned mine = a.lrc[tb * FE_LR + lane];
@@ -782,6 +786,7 @@ struct FeCentres { float c[3 * RADIX_MAX_SEG]; };
 struct FeTileArgs {
     FeTab t; FeCentres cen; const FeGeom* geom; const unsigned* tot; const unsigned* boff; unsigned* nocc; unsigned char* lrc; unsigned char* flag;
     unsigned* okey; float* odmax; unsigned* ocum; FeItem* work; int* counters; FeTileInfo* info; int num_points, k1_mult, k1_widen;
+    unsigned long long* given;          // fe_scatter_counters when the records are a room plan's and no scatter runs to count them (else NULL): per room, the records the stages were given
 };
 // per stage s = 1..3 a block of 8 counters behind the whole-room ones: [0] items of the stage's work list, [3] the overflow rows' cursor
 __host__ __device__ __forceinline__ int* fe_stage_counters(int* counters, int stage) { return counters + 32 + 8 * (stage - 1); }
@@ -834,7 +839,7 @@ __global__ __launch_bounds__(FE_NT) void fe_tile_order(FeTileArgs a) {
     const FeGeom g = a.geom[r];
     int* cb = fe_stage_counters(a.counters, 1);
     FeTileInfo ti; ti.n = 0; ti.k1 = 0; ti.k2 = 0; ti.stage = 0; ti.reduced = 0; ti.pad0 = ti.pad1 = ti.pad2 = 0;
-    if (!g.ok) { if (tid == 0) a.info[r] = ti; return; }
+    if (!g.ok) { if (tid == 0) a.info[r] = ti; return; }          // (given[r] stays 0: such a room has no record)
     const float* c = a.cen.c + 3 * r;
     const unsigned* tot = a.tot + (size_t)r * FE_NBMAX;
     if (tid == 0) s_n = 0;
@@ -862,7 +867,7 @@ __global__ __launch_bounds__(FE_NT) void fe_tile_order(FeTileArgs a) {
             a.work[(size_t)s_base + atomicAdd(&s_n, 1)] = fe_tile_item(a, g, r, b);
             if (a.flag) a.flag[(size_t)r * FE_NBMAX + b] = 1;
         }
-        if (tid == 0) a.info[r] = ti;
+        if (tid == 0) { a.info[r] = ti; if (a.given) a.given[r] = a.boff[(size_t)r * (FE_NBMAX + 1) + g.nb]; }          // every bucket is flagged: all of the room's records
         return;
     }
     // bitonic network over the next power of two (the padding sorts last); a rank-by-counting pass was tried: n^2 comparisons on ONE compute unit, 347 us
@@ -920,7 +925,8 @@ __global__ __launch_bounds__(FE_NT) void fe_tile_order(FeTileArgs a) {
     // what the pruned scatter goes by: every non-empty bucket's flag, written anew by every call (an empty bucket's is never looked at: no point finds its cursor)
     if (a.flag) for (int i = tid; i < n; i += FE_NT) a.flag[(size_t)r * FE_NBMAX + (s_k[i] & (FE_NBMAX - 1))] = i < k1 ? 1 : 0;
     ti.k1 = k1; ti.k2 = k1; ti.reduced = k1; ti.stage = 1;
-    if (tid == 0) a.info[r] = ti;
+    // what MODE 1 of the scatter would have counted: the points of the flagged buckets = of ranks [0, k1) (ocum: written above, in front of a barrier)
+    if (tid == 0) { a.info[r] = ti; if (a.given) a.given[r] = k1 ? a.ocum[(size_t)r * FE_NBMAX + k1 - 1] : 0u; }
 }
 
 // One workgroup per room between two stages: what the stage before left (exact row counts in nocc) decides the next stage's ranks.
@@ -966,7 +972,10 @@ __global__ __launch_bounds__(FE_NT) void fe_tile_plan(FeTileArgs a) {
         for (int i = tid; i < n; i += FE_NT) v += (key[i] >> FE_TO_KBITS) <= mq ? 1u : 0u;         // ranks whose least distance does not exceed that greatest one (a prefix: the order)
         fe_block_scan(v, s_w, FE_NT, total);
         lo = k1; hi = min(n, max((int)total, k2a));
-        if (tid == 0) { a.info[r].k2 = hi; a.info[r].reduced = hi; a.info[r].stage = 2; }
+        if (tid == 0) {
+            a.info[r].k2 = hi; a.info[r].reduced = hi; a.info[r].stage = 2;
+            if (a.given) a.given[r] += cum[n - 1] - (k1 ? cum[k1 - 1] : 0u);          // what MODE 2 would have counted: the points of the room's unflagged buckets, ranks [k1, n)
+        }
     } else {
         const int k2 = ti.k2;
         if (k2 >= n) return;
@@ -1022,8 +1031,15 @@ void fe_launch_tables(const FeTab& t, const float* d_p, float dl, GsParams* prm,
 
 // A room plan: the tables of fe_launch_tables in buffers of its own (not the per-stream scratch: calls on any stream read them, a call without a plan on the same
 // stream does not touch them), and the identity of what they were built from.  Read-only once built.
+// It also holds the rooms' records: where a record lands follows from the rooms' points and dl alone (boff, cntm), and a record is the input row itself, so the
+// every-bucket scatter (MODE 0) runs once, at build, and a call with such a plan launches no scatter and reads none of points / features / labels: fe_reduce reads
+// the plan's records in place (it never writes them: its rows go to the per-stream rows region).  The plan holds the inputs rearranged and counts of them, never a
+// sum or a vote.  Switches, read when a plan is created: SSDR_FE_PLAN_RECORDS=0 builds a plan without records (calls scatter per step as without them: A/B runs);
+// SSDR_FE_PLAN_RECORDS_MAX_MB (default 4096): a plan whose records would be larger is built without them.  Under SSDR_FE_IMAGE=1 (the LDS-image reduction writes a
+// bucket's rows over its records) a call keeps scattering into the per-stream buffer and leaves the plan's records alone.
 struct FePlan {
     DevBuf partial, geom, cntm, tot, boff, items, counters, prm;
+    DevBuf rec; size_t record_bytes = 0;          // the rooms' records, every bucket's where (boff, cntm) put them: 32 B x n_total, or none (record_bytes 0: calls scatter per step)
     const float* d_p = nullptr; const float* d_f = nullptr; const int32_t* d_c = nullptr; size_t fdim = 0, ldim = 0, nr = 0; float dl = 0.f;
     std::vector<int64_t> room_off; FeTab t;
     hipStream_t stream = nullptr; hipEvent_t built = nullptr;          // the stream the tables were built on; recorded behind the last of their launches
@@ -1035,7 +1051,10 @@ struct FePlan {
 
 bool frontend_fits(size_t fdim, size_t ldim) { return 3 + fdim + ldim <= 7; }
 
-// the five launches of fe_launch_tables into a new plan's buffers, on `s`; the event lets a call on another stream wait for them
+// (environment switches of a plan are read at every creation, not once per process: a test sets them in-process)
+static long fe_env_long(const char* name, long dflt) { const char* e = getenv(name); return e && e[0] ? atol(e) : dflt; }
+
+// the five launches of fe_launch_tables into a new plan's buffers, on `s`, and the every-bucket scatter into its records; the event lets a call on another stream wait for them
 int frontend_plan_build(const float* d_p, const float* d_f, size_t fdim, const int32_t* d_c, size_t ldim, const int64_t* room_off, size_t nr, float dl, hipStream_t s,
                         FePlan** out) {
     std::unique_ptr<FePlan> P(new FePlan);
@@ -1046,7 +1065,22 @@ int frontend_plan_build(const float* d_p, const float* d_f, size_t fdim, const i
     SSDR_TRY(P->cntm.reserve(4 * (size_t)FE_NBMAX * t.chunks_max * nr)); SSDR_TRY(P->tot.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(P->boff.reserve(4 * (size_t)(FE_NBMAX + 1) * nr));
     SSDR_TRY(P->items.reserve(sizeof(FeItem) * (size_t)FE_NBMAX * nr)); SSDR_TRY(P->prm.reserve(sizeof(GsParams) * nr));
     SSDR_HIP(hipEventCreateWithFlags(&P->built, hipEventDisableTiming));
+    const size_t rec_bytes = 32 * (size_t)t.n_total;
+    const long max_mb = fe_env_long("SSDR_FE_PLAN_RECORDS_MAX_MB", 4096);
+    const bool records = fe_env_long("SSDR_FE_PLAN_RECORDS", 1) != 0 && max_mb > 0 && rec_bytes <= (size_t)max_mb << 20;
+    if (records) SSDR_TRY(P->rec.reserve(rec_bytes));
     fe_launch_tables(t, d_p, dl, P->prm.as<GsParams>(), P->tables(), P->counters.as<int>(), s);
+    if (records) {
+        // every record of every room with a grid (a room without one writes nothing), behind fe_bscan: the layout a call's own scatter would give
+        const FeTables T = P->tables();
+        if (fdim == 3 && ldim == 1)
+            hipLaunchKernelGGL((fe_scatter<3, 1, 0>), dim3(t.chunks_max, (unsigned)nr), dim3(FE_SNT), 0, s, t, d_p, d_f, (int)fdim, (const int*)d_c, (int)ldim, (const FeGeom*)T.geom,
+                               (const unsigned*)T.cntm, (const unsigned*)T.boff, P->rec.as<uint4>(), (const unsigned char*)nullptr, (const FeTileInfo*)nullptr, (unsigned long long*)nullptr);
+        else
+            hipLaunchKernelGGL((fe_scatter<-1, -1, 0>), dim3(t.chunks_max, (unsigned)nr), dim3(FE_SNT), 0, s, t, d_p, d_f, (int)fdim, (const int*)d_c, (int)ldim, (const FeGeom*)T.geom,
+                               (const unsigned*)T.cntm, (const unsigned*)T.boff, P->rec.as<uint4>(), (const unsigned char*)nullptr, (const FeTileInfo*)nullptr, (unsigned long long*)nullptr);
+        P->record_bytes = rec_bytes;
+    }
     SSDR_HIP(hipGetLastError());
     SSDR_HIP(hipEventRecord(P->built, s));
     *out = P.release();
@@ -1060,6 +1094,12 @@ int frontend_plan_destroy(FePlan* P) {
     delete P;
     if (e != hipSuccess) { set_error("rooms_plan_destroy: hipDeviceSynchronize failed: %s", hipGetErrorString(e)); return SSDR_ERR_HIP; }
     return SSDR_OK;
+}
+
+// what a plan holds beside its tables: the bytes of its records (0: none), and whether they are ordered inside a bucket (never, so far)
+void frontend_plan_info(const FePlan* P, int64_t* record_bytes, int32_t* sorted) {
+    if (record_bytes) *record_bytes = (int64_t)P->record_bytes;
+    if (sorted) *sorted = 0;
 }
 
 // the plan answers for exactly the inputs it was built from
@@ -1101,7 +1141,10 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
     SSDR_TRY(S.nocc.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.trow.reserve(4 * (size_t)FE_NBMAX * nr));
     SSDR_TRY(S.lrc.reserve((size_t)FE_NBMAX * FE_LR * nr)); SSDR_TRY(S.pre.reserve(2 * (size_t)FE_NBMAX * FE_LR * nr));
     SSDR_TRY(S.rowcnt.reserve(4 * (size_t)FE_ROWCAP * nr));
-    SSDR_TRY(S.rec.reserve(32 * ((size_t)t.n_total + t.ovf_cap) + 64));
+    // the records are the plan's: no scatter in this call, and the per-stream buffer holds the rows region alone (the LDS-image variant writes rows over records:
+    // it keeps its own scatter into the per-stream buffer)
+    const bool plan_rec = plan && plan->record_bytes && !fe_image;
+    SSDR_TRY(S.rec.reserve(32 * ((plan_rec ? 0 : (size_t)t.n_total) + t.ovf_cap) + 64));
     if (!S.rcp_ready) {
         SSDR_TRY(S.rcp.reserve(4 * (FE_CAP + 1)));
         hipLaunchKernelGGL(fe_rcp_init, dim3((FE_CAP + 256) / 256), dim3(256), 0, s, S.rcp.as<float>());
@@ -1113,7 +1156,8 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
     const FeTables T = plan ? plan->tables() : own;
     const FeGeom* geom = T.geom; int* counters = S.counters.as<int>(); const FeItem* items = T.items;
     const unsigned* cntm = T.cntm; const unsigned* tot = T.tot; const unsigned* boff = T.boff;
-    FeRedArgs ra; ra.t = t; ra.items = items; ra.prm = prm; ra.counters = counters; ra.rcp = S.rcp.as<float>(); ra.rec = S.rec.as<uint4>();
+    FeRedArgs ra; ra.t = t; ra.items = items; ra.prm = prm; ra.counters = counters; ra.rcp = S.rcp.as<float>();
+    ra.rec = plan_rec ? plan->rec.as<uint4>() : S.rec.as<uint4>(); ra.rows = S.rec.as<uint4>() + (plan_rec ? 0 : 2 * (size_t)t.n_total); ra.wrec = S.rec.as<uint4>();
     ra.nocc = S.nocc.as<unsigned>(); ra.trow = S.trow.as<unsigned>(); ra.lrc = S.lrc.as<unsigned char>(); ra.fdim = (int)fdim; ra.ldim = (int)ldim;
     // the staged reduction (centres given).  Stage 1's buckets follow from the buckets' point counts, their boxes and the centres: all there after fe_bscan, so the
     // order comes first and the scatter writes the records of those buckets only.  SSDR_FE_SCATTER_PRUNE=0 (development: A/B runs in one build) keeps the one
@@ -1136,6 +1180,8 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
         // 7 the same as 6; two calls 3.149-3.176): a stage costs the latency of a bucket's reduction (~100 us) however few buckets it holds, so the
         // first stage should usually be the last.  With the pruned scatter a smaller stage 1 also saves scattered writes, and a miss costs a second read of the room.
         ta.k1_mult = k1_mult; ta.k1_widen = k1_mult != 2;
+        // no scatter counts its records when they are the plan's: the order and the stage plan count what the stages are given, into the same words
+        ta.given = prune && plan_rec ? fe_scatter_counters(counters) : nullptr;
     }
     const unsigned char* flag = S.flag.as<unsigned char>(); const FeTileInfo* tinfo = S.tinfo.as<FeTileInfo>(); unsigned long long* nscat = fe_scatter_counters(counters);
     // profiler sites (ssdr_prof_enable; bench.py's roofline leg): `work` = the algorithmic bytes a site is charged with — the one read of the inputs
@@ -1161,7 +1207,7 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
             hipLaunchKernelGGL((fe_scatter<-1, -1, MODE>), dim3(t.chunks_max, R), dim3(FE_SNT), 0, s, t, d_p, d_f, (int)fdim, (const int*)d_c, (int)ldim, geom, cntm, \
                                boff, S.rec.as<uint4>(), flag, tinfo, nscat);                                                                                \
     } while (0)
-    {
+    if (!plan_rec) {
     ProfScope prof("fe_scatter", s, (double)(12 + 4 * (fdim + ldim)) * (double)t.n_total);
     if (prune) FE_LAUNCH_SCATTER(1);
     else FE_LAUNCH_SCATTER(0);
@@ -1178,7 +1224,7 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
             else if (stage == 2) {
                 hipLaunchKernelGGL((fe_tile_plan<2>), dim3(R), dim3(FE_NT), 0, s, ta);
                 // the records stage 1 did not need, for the rooms that go on (a second read of their points); every other room's workgroups leave at once
-                if (prune) FE_LAUNCH_SCATTER(2);
+                if (prune && !plan_rec) FE_LAUNCH_SCATTER(2);
             }
             else hipLaunchKernelGGL((fe_tile_plan<3>), dim3(R), dim3(FE_NT), 0, s, ta);
             ra.counters = fe_stage_counters(counters, stage);
@@ -1204,7 +1250,7 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
     ProfScope prof_move("fe_rows_move", s, 0.0);
     hipLaunchKernelGGL(fe_rowpre, dim3(256, R), dim3(BS), 0, s, geom, boff, S.lrc.as<unsigned char>(), S.pre.as<unsigned short>(), S.rowcnt.as<unsigned>());
     hipLaunchKernelGGL(fe_rowscan, dim3(R), dim3(FE_NT), 0, s, geom, S.rowcnt.as<unsigned>(), prm, (long long*)d_om);
-    FeMoveArgs ma; ma.t = t; ma.geom = geom; ma.items = items; ma.counters = counters; ma.rec = S.rec.as<uint4>(); ma.nocc = S.nocc.as<unsigned>();
+    FeMoveArgs ma; ma.t = t; ma.geom = geom; ma.items = items; ma.counters = counters; ma.rec = ra.wrec; ma.rows = ra.rows; ma.nocc = S.nocc.as<unsigned>();
     ma.trow = S.trow.as<unsigned>(); ma.lrc = S.lrc.as<unsigned char>(); ma.pre = S.pre.as<unsigned short>(); ma.rowbase = S.rowcnt.as<unsigned>(); ma.fdim = (int)fdim; ma.ldim = (int)ldim;
     ma.out_p = d_op; ma.out_f = d_of; ma.out_c = d_oc;
     // a wave per item, round robin: 8 workgroups per CU give every wave two items of different sizes, 32 one (0.100 -> 0.094 ms; SSDR_FE_MOVE_WGS)

@@ -546,6 +546,7 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
 int frontend_plan_build(const float* d_p, const float* d_f, size_t fdim, const int32_t* d_c, size_t ldim, const int64_t* room_off, size_t nr, float dl, hipStream_t s,
                         FePlan** out);
 int frontend_plan_destroy(FePlan* plan);
+void frontend_plan_info(const FePlan* plan, int64_t* record_bytes, int32_t* sorted);
 int frontend_plan_check(const FePlan* plan, const float* d_p, const float* d_f, size_t fdim, const int32_t* d_c, size_t ldim, const int64_t* room_off, size_t nr, float dl);
 int frontend_tile_stats(hipStream_t s, int32_t* stage, int32_t* reduced, int32_t* buckets, size_t nr);
 void frontend_tile_forget(hipStream_t s);
@@ -704,6 +705,13 @@ int ssdr_rooms_plan_destroy(void* plan) {
     if (!plan) return SSDR_OK;
     SSDR_TRY(ensure_init());
     return frontend_plan_destroy(static_cast<FePlan*>(plan));
+}
+
+/* what the plan holds beside its tables (no device work): the bytes of its records, 0 = none; whether they are ordered inside a bucket */
+int ssdr_rooms_plan_info(void* plan, int64_t* out_record_bytes, int32_t* out_sorted) {
+    if (!plan) { set_error("rooms_plan_info: no plan"); return SSDR_ERR_INVALID; }
+    frontend_plan_info(static_cast<const FePlan*>(plan), out_record_bytes, out_sorted);
+    return SSDR_OK;
 }
 
 /* ssdr_tile_from_rooms_batch_dev over the rooms `plan` was built from: the same outputs, status and stats bit for bit.  Under SSDR_SUBSAMPLE_SORT the plan is

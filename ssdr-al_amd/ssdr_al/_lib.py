@@ -131,6 +131,7 @@ def lib():
         L.ssdr_tile_from_rooms_batch_dev.argtypes = [vp, vp, sz, vp, sz, vp, sz, f32, vp, vp, vp, vp, vp, sz, vp, vp, f32, vp, vp, vp, vp, vp]
         L.ssdr_rooms_plan_create_dev.argtypes = [vp, vp, sz, vp, sz, vp, sz, f32, vp, C.POINTER(vp)]
         L.ssdr_rooms_plan_destroy.argtypes = [vp]
+        L.ssdr_rooms_plan_info.argtypes = [vp, vp, vp]
         L.ssdr_tile_from_rooms_planned_batch_dev.argtypes = [vp] + L.ssdr_tile_from_rooms_batch_dev.argtypes
         L.ssdr_tile_from_rooms_stats.argtypes = [vp, vp, vp, vp, sz]
         L.ssdr_tile_from_rooms_scatter_stats.argtypes = [vp, vp, vp, sz]
