@@ -353,6 +353,31 @@ int ssdr_predict_translate_dev(const int64_t* cloud_offsets, size_t num_clouds, 
 int ssdr_predict_readback_dev(const int64_t* cloud_offsets, size_t num_clouds, size_t num_points, size_t num_layers, const int32_t* ratios,
                               const int32_t* d_cm_idx, const float* d_pk_probs, size_t num_classes, const float* d_pk_feat32, int mode,
                               float* d_probs, float* d_feat32, void* stream);
+/* The Semantic3D flavour (Semantic3D_Dataset_Sampling in mode "sampling", SSRD_AL_semantic3d/semantic3d_dataset_sampling.py:114-294;
+ * total[point_idx[0]] = out, sampler2.py:344, :629): a scan is never padded, ssdr_split3_dev cuts its tile into parts, and every combined part
+ * is one cloud of the layout above with num_points = 1 (T = the part's rows): ssdr_predict_layout, ssdr_knn_pyramid_ragged_dev,
+ * ssdr_predict_translate_dev and ssdr_randla_infer_rows_dev take the part offsets as cloud_offsets and num_points = 1.
+ * ssdr_predict_scan_tile_dev: the tile of ONE scan of n points (at most 0x3fffffff), tile.hip's rule with num_points = n: all rows by ascending
+ *   float32 squared distance to center[3] (host), ties by index, row r = sorted position d_perm[r] (a permutation of [0, n)), minus the centre
+ *   on all three axes.  d_t_xyz [n,3], d_t_idx [n] (the reference's queried_idx), d_t_feat [n,6] = [xyz, rgb * color_scale] (8-byte aligned;
+ *   ssdr_feed_augment_dev with one tile of n rows then rewrites columns 0..2).
+ * ssdr_predict_parts_dev: the parts of one chunk as ragged clouds.  d_t_xyz / d_t_feat / d_t_idx: the tiles of all scans, concatenated in scan
+ *   order (scan c's rows start at its first point, T_c = n_c); d_order: ssdr_split3_dev's output of every scan at the same offsets (values are
+ *   scan-local tile rows); part_offsets host int64 [num_parts + 1]: the chunk's parts as ranges of d_order (absolute, the first need not be 0);
+ *   part_base host int64 [num_parts]: the first point of each part's scan; d_labels i32 [sum n_c] in point order (may be NULL).  With
+ *   row = part_base[k] + d_order[part_offsets[k] + j]: d_cm_xyz [rows,3] part-major (ssdr_knn_pyramid_ragged_dev's input), and at packed position
+ *   pos(k, j): d_pk_xyz = d_t_xyz[row], d_pk_feat = d_t_feat[row], d_pk_src = part_base[k] + d_t_idx[row] (the point, over all scans; the sum
+ *   of all n_c must stay below 2^30), d_pk_labels = d_labels[d_pk_src] (may be NULL).  Refusals: as ssdr_predict_layout, with "cloud" = part.
+ * ssdr_predict_scatter_dev: d_probs[d_pk_src[r]] = d_pk_probs[r] and d_feat32 likewise for r < num_rows (d_probs [num_out, num_classes],
+ *   d_feat32 [num_out, 32], both feature arrays 16-byte aligned).  Every point lies in exactly one part: one writer per output row, no atomic,
+ *   no order dependence.  A source outside [0, num_out) writes nothing.  All three only enqueue. */
+int ssdr_predict_scan_tile_dev(const float* d_points, const float* d_colors, size_t n, const float* center, const int32_t* d_perm, float color_scale,
+                               float* d_t_xyz, float* d_t_feat, int32_t* d_t_idx, void* stream);
+int ssdr_predict_parts_dev(const float* d_t_xyz, const float* d_t_feat, const int32_t* d_t_idx, const int32_t* d_labels, const int32_t* d_order,
+                           const int64_t* part_offsets, const int64_t* part_base, size_t num_parts, size_t num_layers, const int32_t* ratios,
+                           float* d_cm_xyz, float* d_pk_xyz, float* d_pk_feat, int32_t* d_pk_src, int32_t* d_pk_labels, void* stream);
+int ssdr_predict_scatter_dev(const int32_t* d_pk_src, size_t num_rows, const float* d_pk_probs, size_t num_classes, const float* d_pk_feat32,
+                             size_t num_out, float* d_probs, float* d_feat32, void* stream);
 
 /* ---- selection stage (replaces the NumPy / sklearn host code of S3/sampler2.py:12-47,102-115,262-266,313-342,
  *      612-640, S3/fps_gcn_cpu.py:12-178 and S3/kcenterGreedy.py:60-128) ---------------------------------------
@@ -678,7 +703,9 @@ int ssdr_confusion_dev(const float* d_probs, int num_classes, const int32_t* d_p
  *   differs from the last call's on that stream).  The map comes out bit for bit the same on every run.
  * Refused before anything is launched: no clouds, an empty cloud, num_tiles or num_points 0, d_out_labels without d_labels
  * (SSDR_ERR_INVALID); more than 4096 clouds, more than 0x3fffffff points or tile rows in all (SSDR_ERR_UNSUPPORTED).
- * ssdr_vote_tile_launches: kernel launches ssdr_vote_tiles_dev makes per tile (plus one per call). */
+ * ssdr_vote_tile_launches: kernel launches ssdr_vote_tiles_dev makes per tile (plus one per call).
+ * The Semantic3D flavour (Semantic3D_Dataset_Test.get_batch, semantic3d_dataset_test3.py:143-192) is ssdr_feed_chain_dev with flags =
+ * SSDR_FEED_XY_ONLY | SSDR_FEED_GLOBAL_ROWS, no class weights and no channels, followed by ssdr_feed_augment_dev over the batch. */
 int ssdr_vote_init_dev(const double* d_possibility, const int64_t* cloud_offsets, size_t num_clouds, double* d_cloud_min, int32_t* d_cloud_arg,
                        void* stream);
 int ssdr_vote_tiles_dev(const float* d_points, const float* d_colors, int color_dim, const int32_t* d_labels, double* d_possibility,

@@ -23,6 +23,11 @@
 //   predict_rb_keys      "reference" on padded clouds: (cloud << kb | source index) words, row as value; the stable radix sort orders them
 //   predict_rb_sorted    ... and the p-th smallest key's row becomes point p's (argsort(point_idx)[p], stable)
 //   predict_rb_gather    probs / feat32 rows -> cloud order
+// The Semantic3D flavour (whole scans, never padded, cut into parts by split3; further down):
+//   scan_keys            distance bits per point of one scan, the stable radix sort orders them by (distance, index)
+//   scan_gather          tile.hip's gather without the padding branch: t_xyz, t_idx, t_feat = [xyz, rgb * scale] in tile-row order
+//   parts_gather         the parts of a chunk as ragged clouds: part-major xyz, then xyz / features / source point / label at their packed positions
+//   predict_scatter      total[point_idx] = out: packed probs / feat32 rows -> the points they belong to, one writer per row
 #include "ssdr_internal.hpp"
 #include "tile_body.hpp"
 #include <cmath>
@@ -102,8 +107,8 @@ int make_pack(const char* who, const int64_t* cloud_offsets, size_t num_clouds, 
 
 // one staging ring per entry point: a ring slot is reused SLOTS calls later, after waiting for its copy to have executed, so with one ring
 // per entry a caller can keep SLOTS chunks in flight on a stream before the host waits for the device
-enum { STG_TILE, STG_TRANSLATE, STG_READBACK };
-struct PredictState { DevBuf tab, keys, vals, padmap, rb_rows; RadixSorter sorter; StagingRing<int> staging[3]; };
+enum { STG_TILE, STG_TRANSLATE, STG_READBACK, STG_PARTS };
+struct PredictState { DevBuf tab, keys, vals, padmap, rb_rows; RadixSorter sorter; StagingRing<int> staging[4]; };
 PredictState& pst(hipStream_t s) { return per_stream<PredictState>(s); }
 
 int upload_tab(PredictState& S, const Pack& p, hipStream_t s, int which) {
@@ -233,6 +238,72 @@ __global__ __launch_bounds__(256) void predict_rb_gather(const int* __restrict__
     }
 }
 
+// ---- Semantic3D flavour: a whole scan, never padded, cut into parts that run as ragged clouds -------------------------------------------
+// Reference: Semantic3D_Dataset_Sampling in mode "sampling" (semantic3d_dataset_sampling.py:114-155: query(k = len(points)), shuffle, centre on
+// all three axes), tf_map's split3 + merge (:198-294: one pyramid and one network call per part) and total[point_idx[0]] = out
+// (sampler2.py:344, :629).  The tile of a scan is tile.hip's rule with num_points = n and no padding; a part is a "cloud" of the packing
+// above with num_points = 1 (T = its rows), so the pyramid, the translation and the network run as they do for whole rooms.
+
+// word = the distance bits (31: tile_dist clears the sign), value = the point: the stable sort gives (distance, index) order
+__global__ __launch_bounds__(256) void scan_keys(int n, const float* __restrict__ pts, float cx, float cy, float cz, uint64_t* keys, uint32_t* vals) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        keys[i] = (uint64_t)__float_as_uint(tile_dist(pts, i, cx, cy, cz));
+        vals[i] = (uint32_t)i;
+    }
+}
+
+// tile_gather_body's unpadded branch: row r takes sorted position perm[r]; features [xyz, rgb * scale] (ssdr_feed_augment_dev rewrites columns 0..2)
+__global__ __launch_bounds__(256) void scan_gather(int n, const float* __restrict__ pts, const float* __restrict__ colors, const uint32_t* __restrict__ sorted,
+                                                   const int* __restrict__ perm, float cx, float cy, float cz, float color_scale,
+                                                   float* t_xyz, float* t_feat, int* t_idx) {
+    for (int r = blockIdx.x * 256 + threadIdx.x; r < n; r += gridDim.x * 256) {
+        const int pos = min(max(perm[r], 0), n - 1);                   // a permutation of [0, n) by contract: never read past the scan
+        const size_t id = sorted[pos];
+        const float x = pts[3 * id] - cx, y = pts[3 * id + 1] - cy, z = pts[3 * id + 2] - cz;
+        t_xyz[3 * (size_t)r] = x; t_xyz[3 * (size_t)r + 1] = y; t_xyz[3 * (size_t)r + 2] = z;
+        float2* f = reinterpret_cast<float2*>(t_feat + 6 * (size_t)r);          // 24-byte rows: three 8-byte stores
+        f[0] = make_float2(x, y);
+        f[1] = make_float2(z, colors[3 * id] * color_scale);
+        f[2] = make_float2(colors[3 * id + 1] * color_scale, colors[3 * id + 2] * color_scale);
+        t_idx[r] = (int)id;
+    }
+}
+
+// blockIdx.y = part, one work-item per row.  order[ro + j] is the scan-local tile row of the part's j-th row (ascending inside a part: the
+// reads walk forward through the scan's tile, the part-major writes are contiguous, the packed ones contiguous per segment).
+__global__ __launch_bounds__(256) void parts_gather(const int* __restrict__ tab, int W, int L, const int* __restrict__ base, const float* __restrict__ t_xyz,
+                                                    const float* __restrict__ t_feat, const int* __restrict__ t_idx, const int* __restrict__ labels,
+                                                    const int* __restrict__ order, float* cm_xyz, float* pk_xyz, float* pk_feat, int* pk_src, int* pk_lab) {
+    const int c = blockIdx.y;
+    const int* t = tab + (size_t)c * W;
+    const int n = t[PT_N], ro = t[PT_ROW], b = base[c];
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) {
+        const size_t q = (size_t)ro + j, row = (size_t)b + order[q], p = (size_t)packed_pos(t, L, j);
+        const float x = t_xyz[3 * row], y = t_xyz[3 * row + 1], z = t_xyz[3 * row + 2];
+        cm_xyz[3 * q] = x; cm_xyz[3 * q + 1] = y; cm_xyz[3 * q + 2] = z;
+        pk_xyz[3 * p] = x; pk_xyz[3 * p + 1] = y; pk_xyz[3 * p + 2] = z;
+        const float2* fi = reinterpret_cast<const float2*>(t_feat + 6 * row);
+        float2* fo = reinterpret_cast<float2*>(pk_feat + 6 * p);
+        fo[0] = fi[0]; fo[1] = fi[1]; fo[2] = fi[2];
+        const int src = b + t_idx[row];
+        pk_src[p] = src;
+        if (pk_lab) pk_lab[p] = labels[src];
+    }
+}
+
+// total[point_idx] = out: eight lanes per packed row, a 16-byte piece of the 128-byte feature row each and every eighth class of the
+// probabilities.  Every point lies in exactly one part, so every output row has one writer.  A source outside [0, num_out) writes nothing.
+__global__ __launch_bounds__(256) void predict_scatter(const int* __restrict__ src, long rows, long num_out, const float* __restrict__ pk_probs, int C,
+                                                       const float* __restrict__ pk_feat, float* probs, float* feat) {
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < rows * 8; e += (long)gridDim.x * 256) {
+        const long r = e >> 3; const int lane = (int)(e & 7);
+        const long d = src[r];
+        if (d < 0 || d >= num_out) continue;
+        reinterpret_cast<float4*>(feat)[d * 8 + lane] = reinterpret_cast<const float4*>(pk_feat)[r * 8 + lane];
+        for (int ch = lane; ch < C; ch += 8) probs[d * C + ch] = pk_probs[r * C + ch];
+    }
+}
+
 }  // namespace
 }  // namespace ssdr
 
@@ -355,6 +426,73 @@ int ssdr_predict_readback_dev(const int64_t* cloud_offsets, size_t num_clouds, s
         const int g = (int)std::max(1.0, std::min(std::ceil(el / 256.0), (double)ctx().num_cu * 16));
         hipLaunchKernelGGL(predict_rb_gather, dim3(g), dim3(256), 0, s, S.rb_rows.as<int>(), (long)p.points, d_pk_probs, (int)num_classes, d_pk_feat32, d_probs, d_feat32);
     }
+    SSDR_HIP(hipGetLastError());
+    return SSDR_OK;
+}
+
+int ssdr_predict_scan_tile_dev(const float* d_points, const float* d_colors, size_t n, const float* center, const int32_t* d_perm, float color_scale,
+                               float* d_t_xyz, float* d_t_feat, int32_t* d_t_idx, void* stream) {
+    if (!d_points || !d_colors || !center || !d_perm || !d_t_xyz || !d_t_feat || !d_t_idx || ((uintptr_t)d_t_feat & 7)) {
+        set_error("predict_scan_tile: bad arguments"); return SSDR_ERR_INVALID;
+    }
+    if (n == 0) { set_error("predict_scan_tile: the scan is empty (every scan needs at least one point)"); return SSDR_ERR_INVALID; }
+    if (n > 0x3fffffffull) { set_error("predict_scan_tile: %zu points in one scan (at most 0x3fffffff)", n); return SSDR_ERR_UNSUPPORTED; }
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream); PredictState& S = pst(s);
+    SSDR_TRY(S.keys.reserve(8 * n + 16)); SSDR_TRY(S.vals.reserve(4 * n + 16));
+    const int g = (int)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, (size_t)ctx().num_cu * 16));
+    {
+        ProfScope prof("predict_scan_keys", s, 24.0 * (double)n);
+        hipLaunchKernelGGL(scan_keys, dim3(g), dim3(256), 0, s, (int)n, d_points, center[0], center[1], center[2], S.keys.as<uint64_t>(), S.vals.as<uint32_t>());
+    }
+    S.sorter.wide_high = true;
+    const int off[2] = {0, (int)((n + RADIX_TILE - 1) / RADIX_TILE * RADIX_TILE)}, nh = (int)n;
+    SSDR_TRY(S.sorter.sort_segments(S.keys.as<uint64_t>(), S.vals.as<uint32_t>(), 1, off, &nh, nullptr, s, 31));
+    {
+        ProfScope prof("predict_scan_gather", s, (double)n * (4 + 4 + 12 + 12 + 12 + 24 + 4));
+        hipLaunchKernelGGL(scan_gather, dim3(g), dim3(256), 0, s, (int)n, d_points, d_colors, S.vals.as<uint32_t>(), d_perm, center[0], center[1], center[2],
+                           color_scale, d_t_xyz, d_t_feat, d_t_idx);
+    }
+    SSDR_HIP(hipGetLastError());
+    return SSDR_OK;
+}
+
+int ssdr_predict_parts_dev(const float* d_t_xyz, const float* d_t_feat, const int32_t* d_t_idx, const int32_t* d_labels, const int32_t* d_order,
+                           const int64_t* part_offsets, const int64_t* part_base, size_t num_parts, size_t num_layers, const int32_t* ratios,
+                           float* d_cm_xyz, float* d_pk_xyz, float* d_pk_feat, int32_t* d_pk_src, int32_t* d_pk_labels, void* stream) {
+    if (!d_t_xyz || !d_t_feat || !d_t_idx || !d_order || !part_base || !d_cm_xyz || !d_pk_xyz || !d_pk_feat || !d_pk_src || (d_pk_labels && !d_labels) ||
+        ((uintptr_t)d_t_feat & 7) || ((uintptr_t)d_pk_feat & 7)) {
+        set_error("predict_parts: bad arguments"); return SSDR_ERR_INVALID;
+    }
+    Pack p;
+    SSDR_TRY(make_pack("predict_parts", part_offsets, num_parts, 1, num_layers, ratios, p));
+    for (int c = 0; c < p.nc; ++c)
+        if (part_base[c] < 0 || part_base[c] > 0x7fffffffLL - 0x40000000LL) { set_error("predict_parts: part %d: its scan starts at point %lld (int32 sources)", c, (long long)part_base[c]); return SSDR_ERR_UNSUPPORTED; }
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream); PredictState& S = pst(s);
+    const int W = tab_w(p.L), nc = p.nc;
+    for (int c = 0; c < nc; ++c) p.tab.push_back((int)part_base[c]);        // the scans' first rows ride behind the part table
+    SSDR_TRY(upload_tab(S, p, s, STG_PARTS));
+    const int* tab = S.tab.as<int>();
+    ProfScope prof("predict_parts_gather", s, (double)p.rows * (4 + 12 + 24 + 4 + 12 + 12 + 24 + 4 + (d_pk_labels ? 8 : 0)));
+    hipLaunchKernelGGL(parts_gather, dim3(std::max(1, std::min((p.max_t + 255) / 256, 256)), nc), dim3(256), 0, s, tab, W, p.L, tab + (size_t)nc * W, d_t_xyz, d_t_feat,
+                       d_t_idx, d_labels, d_order + part_offsets[0], d_cm_xyz, d_pk_xyz, d_pk_feat, d_pk_src, d_pk_labels);
+    SSDR_HIP(hipGetLastError());
+    return SSDR_OK;
+}
+
+int ssdr_predict_scatter_dev(const int32_t* d_pk_src, size_t num_rows, const float* d_pk_probs, size_t num_classes, const float* d_pk_feat32,
+                             size_t num_out, float* d_probs, float* d_feat32, void* stream) {
+    if (!d_pk_src || !d_pk_probs || !d_pk_feat32 || !d_probs || !d_feat32 || num_rows == 0 || num_classes == 0 || num_classes > 1024 ||
+        ((uintptr_t)d_pk_feat32 & 15) || ((uintptr_t)d_feat32 & 15)) {
+        set_error("predict_scatter: bad arguments"); return SSDR_ERR_INVALID;
+    }
+    if (num_rows > SSDR_PREDICT_MAX_ROWS) { set_error("predict_scatter: %zu packed rows (cap %d = 2^23)", num_rows, SSDR_PREDICT_MAX_ROWS); return SSDR_ERR_UNSUPPORTED; }
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream);
+    ProfScope prof("predict_scatter", s, (double)num_rows * (4.0 + 8.0 * (double)(num_classes + 32)));
+    const int g = (int)std::max<size_t>(1, std::min<size_t>((num_rows * 8 + 255) / 256, (size_t)ctx().num_cu * 16));
+    hipLaunchKernelGGL(predict_scatter, dim3(g), dim3(256), 0, s, d_pk_src, (long)num_rows, (long)num_out, d_pk_probs, (int)num_classes, d_pk_feat32, d_probs, d_feat32);
     SSDR_HIP(hipGetLastError());
     return SSDR_OK;
 }

@@ -170,6 +170,9 @@ def lib():
         L.ssdr_knn_pyramid_ragged_dev.argtypes = [vp, vp, sz, sz, sz, vp, sz, vp, vp, vp]
         L.ssdr_predict_translate_dev.argtypes = [vp, sz, sz, sz, vp, sz, vp, vp, vp, vp, vp]
         L.ssdr_predict_readback_dev.argtypes = [vp, sz, sz, sz, vp, vp, vp, sz, vp, i32, vp, vp, vp]
+        L.ssdr_predict_scan_tile_dev.argtypes = [vp, vp, sz, vp, vp, f32, vp, vp, vp, vp]
+        L.ssdr_predict_parts_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+        L.ssdr_predict_scatter_dev.argtypes = [vp, sz, vp, sz, vp, sz, vp, vp, vp]
         _lib = _libs[path] = L
     return _lib
 

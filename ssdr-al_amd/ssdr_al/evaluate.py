@@ -89,23 +89,50 @@ class VoteTester:
     and draw buffers exist DEPTH times); the draws are uploaded on a third stream, so the host waits for the generator of DEPTH
     batches ago only, never for the network.  ``ready`` guards the draw buffers against the upload
     stream.  A draw made on the device needs no event of its own: it is enqueued on the generator's stream in front of the chain,
-    the stream whose chain was the last reader of those buffers, and the set's next upload waits for ``ready`` as before."""
+    the stream whose chain was the last reader of those buffers, and the set's next upload waits for ``ready`` as before.
+
+    ``dataset="Semantic3D"``: Network.evaluate_test_semantic3d (SSRD_AL_semantic3d/RandLANet.py:339-485) over Semantic3D_Dataset_Test.get_batch
+    (semantic3d_dataset_test3.py:129-259).  The generator is the chain's general form (ssdr_feed_chain_dev, flags SSDR_FEED_XY_ONLY |
+    SSDR_FEED_GLOBAL_ROWS, no class weights: queried_pt_weight = 1): x / y centred, z kept, the possibility update over all three axes; the
+    features are tf_augment_input's over the batch (ssdr_feed_augment_dev; ``draw`` gains rot, scale and aug_noise, built as TrainFeeder.draw
+    builds them, aug_noise on the device with ``draws="device"``); colours times ``color_scale``.  ``test_smooth=None`` is 0.95 for S3DIS and
+    0.98 for Semantic3D (:343), ``vote_gap=None`` 1 and 4 (:391): the evaluation runs after the first epoch whose smallest possibility
+    exceeds last_min + vote_gap.  ``config.ignored_label_inds`` (one value; :403-411, :450-458): rows with that label are dropped from both
+    confusions and from OA's count, the other labels shift down by one (done on the host label arrays, as -1 = skipped by
+    ssdr_confusion_dev).  A cloud smaller than num_points is refused."""
 
     DEPTH = 2
 
-    def __init__(self, weights, clouds, config=None, precision="f32", seed=0, num_votes=100, test_smooth=0.95, possibility=None, draws="host"):
+    def __init__(self, weights, clouds, config=None, precision="f32", seed=0, num_votes=100, test_smooth=None, possibility=None, draws="host",
+                 dataset="S3DIS", vote_gap=None, color_scale=1.0):
         from . import randlanet
         if draws not in ("host", "device"):
             raise ValueError("VoteTester: draws must be 'host' or 'device'")
         self.draws = draws
-        from .helper_tool import ConfigS3DIS
-        cfg = self.cfg = ConfigS3DIS if config is None else config
+        if dataset not in ("S3DIS", "Semantic3D"):
+            raise ValueError("VoteTester: dataset must be 'S3DIS' or 'Semantic3D'")
+        self.dataset = dataset
+        sem = self.sem = dataset == "Semantic3D"
+        from .helper_tool import ConfigS3DIS, ConfigSemantic3D
+        cfg = self.cfg = (ConfigSemantic3D if sem else ConfigS3DIS) if config is None else config
         L = _lib.lib()
         _lib.check(L.ssdr_init(0))
-        self.seed, self.num_votes, self.test_smooth = int(seed), num_votes, float(test_smooth)
+        self.seed, self.num_votes = int(seed), num_votes
+        self.test_smooth = float((0.98 if sem else 0.95) if test_smooth is None else test_smooth)
+        self.vote_gap = (4 if sem else 1) if vote_gap is None else vote_gap
+        self.color_scale = float(color_scale)
+        self.augment_noise = float(getattr(cfg, "augment_noise", 0.0)) if sem else 0.0
         self.N, self.B, self.steps, self.C = int(cfg.num_points), int(cfg.val_batch_size), int(getattr(cfg, "val_steps", 100)), int(cfg.num_classes)
         self.nc = len(clouds)
         sizes = [len(c["xyz"]) for c in clouds]
+        if sem and sizes and min(sizes) < self.N:
+            raise ValueError("VoteTester: a Semantic3D cloud of %d points is smaller than num_points = %d (the reference's tree query raises there)"
+                             % (min(sizes), self.N))
+        ignored = list(getattr(cfg, "ignored_label_inds", []) or []) if sem else []
+        if len(ignored) > 1:
+            raise ValueError("VoteTester: ignored_label_inds holds %d values (the reference's labels == ignored_label_inds compares against one)" % len(ignored))
+        # :408-410: rows with the ignored label are dropped (-1: ssdr_confusion_dev skips them), the others shift down by one
+        relabel = (lambda a: np.where(np.asarray(a) == ignored[0], -1, np.asarray(a) - 1)) if ignored else (lambda a: a)
         self.off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         self.n = int(self.off[-1])
         self.has_labels = self.nc > 0 and all(c.get("labels") is not None for c in clouds)
@@ -115,7 +142,7 @@ class VoteTester:
         cat = lambda key, dt, w: (np.concatenate([np.asarray(c[key], dt).reshape(len(c["xyz"]), *w) for c in clouds]) if self.nc else np.zeros((0, *w), dt))
         self.d_points = DevArray.from_host(cat("xyz", np.float32, (3,)))
         self.d_colors = DevArray.from_host(cat("rgb", np.float32, (3,)))
-        self.d_labels = DevArray.from_host(cat("labels", np.int32, ())) if self.has_labels else None
+        self.d_labels = DevArray.from_host(np.ascontiguousarray(relabel(cat("labels", np.int32, ())), np.int32)) if self.has_labels else None
         self.d_poss = DevArray.from_host(poss)
         self.d_cloud_min, self.d_cloud_arg = DevArray((max(self.nc, 1),), np.float64), DevArray((max(self.nc, 1),), np.int32)
         # the raw clouds: global rows of their nearest sub-points, their labels (val_proj, val_labels)
@@ -124,7 +151,7 @@ class VoteTester:
             pi = cl.get("proj_idx")
             proj.append(self.off[c] + (np.arange(sizes[c]) if pi is None else np.asarray(pi, np.int64)))
             rl = cl.get("raw_labels") if pi is not None else cl.get("labels")
-            raw_lab.append(None if rl is None else np.asarray(rl, np.int32))
+            raw_lab.append(None if rl is None else np.asarray(relabel(np.asarray(rl, np.int32)), np.int32))
             self.raw_off.append(self.raw_off[-1] + len(proj[-1]))
         self.n_raw = self.raw_off[-1]
         self.d_proj = DevArray.from_host(np.concatenate(proj).astype(np.int32)) if self.nc else None
@@ -145,6 +172,9 @@ class VoteTester:
                 xyz=DevArray((B, N, 3), np.float32), feat=DevArray((B, N, 6), np.float32), idx=DevArray((B, N), np.int32),
                 labels=DevArray((B, N), np.int32) if self.has_labels else None, cloud=DevArray((B,), np.int32), center=DevArray((B, 3), np.float32),
                 ready=ev(), consumed=ev(), gen_used=False, net_used=False))
+            if sem:
+                self.sets[-1].update(rot=DevArray((B, 2), np.float64), scale=DevArray((B, 3), np.float64),
+                                     aug_noise=DevArray((B, N, 3), np.float64) if self.augment_noise != 0 else None)
         lv = [N]
         for r in cfg.sub_sampling_ratio:
             lv.append(lv[-1] // r)
@@ -180,14 +210,28 @@ class VoteTester:
     def draw(self, epoch, step):
         """the draws of one batch from (seed, epoch, step): noise [B,3] = normal(0, noise_init / 10) cast to float32 (test.py:114-115), one shuffle
         permutation per tile (DP.shuffle_idx, :125), the padding draws of data_aug (:137-141; zeros when no cloud is smaller than a tile).
-        draws="device": the noise alone."""
+        draws="device": the noise alone.  Semantic3D: also rot [B,2] = (cos, sin) of theta = uniform(0, 2 pi), scale [B,3] = uniform(scale_min,
+        scale_max) times the symmetry signs and aug_noise float64 [B,N,3] = normal(0, augment_noise) (None when that is 0), as TrainFeeder.draw
+        builds them (test3.py:220-256); draws="device": without aug_noise."""
         rng = np.random.default_rng([self.seed, int(epoch), int(step)])
-        noise = rng.normal(scale=self.cfg.noise_init / 10, size=(self.B, 3)).astype(np.float32)
-        if self.draws == "device":
-            return dict(noise=noise)
-        perm = np.stack([rng.permutation(self.N) for _ in range(self.B)]).astype(np.int32)
-        dup = rng.random((self.B, self.N), dtype=np.float32) if self.pads else None
-        return dict(noise=noise, perm=perm, dup=dup)
+        cfg, b = self.cfg, self.B
+        host = self.draws == "host"
+        d = dict(noise=rng.normal(scale=cfg.noise_init / 10, size=(b, 3)).astype(np.float32))
+        if host:
+            d.update(perm=np.stack([rng.permutation(self.N) for _ in range(b)]).astype(np.int32),
+                     dup=rng.random((b, self.N), dtype=np.float32) if self.pads else None)
+        if self.sem:
+            theta = rng.uniform(0, 2 * np.pi, size=b)
+            lo, hi = getattr(cfg, "augment_scale_min", 1.0), getattr(cfg, "augment_scale_max", 1.0)
+            s = rng.uniform(lo, hi, size=(b, 3)) if getattr(cfg, "augment_scale_anisotropic", True) else np.repeat(rng.uniform(lo, hi, size=(b, 1)), 3, axis=1)
+            sym = np.ones((b, 3))
+            for i, on in enumerate(getattr(cfg, "augment_symmetries", [False, False, False])):
+                if on:
+                    sym[:, i] = np.round(rng.uniform(size=b)) * 2 - 1
+            d.update(rot=np.stack([np.cos(theta), np.sin(theta)], axis=1), scale=s * sym)
+            if host:
+                d.update(aug_noise=rng.normal(scale=self.augment_noise, size=(b, self.N, 3)) if self.augment_noise != 0 else None)
+        return d
 
     # ---- the two halves of a batch, both enqueue-only ---------------------------------------------------------------------
     def _generate(self, draws, epoch=None, step=None):
@@ -202,6 +246,13 @@ class VoteTester:
         on_device = self.draws == "device"
         ups = [("noise", np.float32)] + ([("perm", np.int32)] if not on_device or draws.get("perm") is not None else [])
         ups += [("dup", np.float32)] if draws.get("dup") is not None else []
+        if self.sem:
+            ups += [("rot", np.float64), ("scale", np.float64)]
+            if draws.get("aug_noise") is not None:
+                if st["aug_noise"] is None:
+                    raise ValueError("VoteTester: augmentation noise drawn, but the config's augment_noise is 0")
+                ups.append(("aug_noise", np.float64))
+        noisy = self.sem and draws.get("aug_noise") is not None
         for k, dt in ups:
             a = np.ascontiguousarray(draws[k], dt)
             assert a.shape == st[k].shape, (k, a.shape, st[k].shape)
@@ -212,8 +263,25 @@ class VoteTester:
                 device_draws.perm(self.seed, epoch, step, self.B, self.N, out=st["perm"], stream=self.s_gen)
             if draws.get("dup") is None and self.pads:
                 device_draws.uniform(self.seed, epoch, step, device_draws.DUP, self.B * self.N, out=st["dup"], stream=self.s_gen)
+            if self.sem and not noisy and self.augment_noise != 0:
+                device_draws.normal(self.seed, epoch, step, device_draws.AUG_NOISE, self.B * self.N * 3, scale=self.augment_noise, out=st["aug_noise"],
+                                    stream=self.s_gen)
+                noisy = True
         if st["net_used"]:
             _lib.check(L.ssdr_stream_wait_event(self.s_gen, st["consumed"]))   # the tile buffers' last reader
+        if self.sem:
+            # get_batch (test3.py:143-192): the chain's general form, x / y centred, global rows, queried_pt_weight = 1; then tf_map's augmentation
+            _lib.check(L.ssdr_feed_chain_dev(self.d_points.ptr, self.d_colors.ptr, 3, self.d_labels.ptr if self.has_labels else None, self.d_poss.ptr,
+                                             self.d_cloud_min.ptr, self.d_cloud_arg.ptr, _lib.ptr(self.off), self.nc, self.B, self.N,
+                                             st["noise"].ptr, st["perm"].ptr, st["dup"].ptr, self.color_scale, st["xyz"].ptr, st["feat"].ptr, st["idx"].ptr,
+                                             st["labels"].ptr if self.has_labels else None, st["cloud"].ptr, st["center"].ptr,
+                                             1 | 2, None, 0, None, None, None, None, self.s_gen))          # SSDR_FEED_XY_ONLY | SSDR_FEED_GLOBAL_ROWS
+            _lib.check(L.ssdr_feed_augment_dev(st["xyz"].ptr, self.B, self.N, st["rot"].ptr, st["scale"].ptr, st["aug_noise"].ptr if noisy else None, 3,
+                                               st["feat"].ptr, self.s_gen))
+            _lib.check(L.ssdr_event_record(st["ready"], self.s_gen))
+            st["gen_used"] = True
+            self._issued += 1
+            return st
         _lib.check(L.ssdr_vote_tiles_dev(self.d_points.ptr, self.d_colors.ptr, 3, self.d_labels.ptr if self.has_labels else None, self.d_poss.ptr,
                                          self.d_cloud_min.ptr, self.d_cloud_arg.ptr, _lib.ptr(self.off), self.nc, self.B, self.N,
                                          st["noise"].ptr, st["perm"].ptr, st["dup"].ptr, 1.0 / 255.0, st["xyz"].ptr, st["feat"].ptr, st["idx"].ptr,
@@ -316,7 +384,8 @@ class VoteTester:
     def evaluate(self, max_epochs=None, draws=None):
         """The loop of RandLANet.py:305-424: whole epochs until the smallest possibility has grown by more than one vote, then the sub-cloud
         confusion rescaled by val_proportions (:353-368), the re-projected confusion, OA and m_IoU (:377-419).  Returns (m_IoU, OA);
-        (0, 0) when max_epochs ends the loop first.  draws: a callable (epoch, step) -> the batch's draws (see draw()) in place of the seeded ones."""
+        (0, 0) when max_epochs ends the loop first.  Semantic3D (SSRD_AL_semantic3d/RandLANet.py:351-485): more than vote_gap votes, last_min
+        becomes new_min, OA = correct / seen over the rows that are not ignored; (m_IoU, 0) when num_votes or max_epochs ends the loop first.  draws: a callable (epoch, step) -> the batch's draws (see draw()) in place of the seeded ones."""
         if self.nc == 0:
             raise ValueError("VoteTester.evaluate: no clouds")
         if not (self.has_labels and self.has_raw_labels):
@@ -332,8 +401,8 @@ class VoteTester:
                 break
             new_min = self._epoch(draws)
             ran += 1
-            if last_min + 1 < new_min:
-                last_min += 1
+            if last_min + self.vote_gap < new_min:
+                last_min = new_min if self.sem else last_min + 1
                 sub_conf, _, _ = self._confusion(None, self.d_labels, self.n)
                 self.sub_confusion = sub_conf
                 Cm = sub_conf.astype(np.float32)                                                       # :362
@@ -341,7 +410,8 @@ class VoteTester:
                 self.sub_ious = _iou_host(Cm)
                 conf, ious, _ = self._confusion(self.d_proj, self._raw_labels, self.n_raw)
                 self.confusion, self.ious = conf, ious
-                oa = int(np.trace(conf)) / float(self.n_raw)                                           # :398-408
+                seen = int(np.sum(self._raw_labels != -1)) if self.sem else self.n_raw                 # len(labels_valid), :464
+                oa = int(np.trace(conf)) / float(seen)                                                 # :398-408
                 m_iou = float(np.mean(ious))                                                           # :411
                 return m_iou, oa
         return m_iou, oa

@@ -354,9 +354,10 @@ class Trainer:
         _lib.check(self._lib.ssdr_randla_train_export(self._h, network._h))
         return network
 
-    def train_round(self, feeder, epochs, tester=None):
-        """``Network.train`` (RandLANet.py:217-282): per epoch the feeder's batches, then the decay; from int(0.4 epochs) on the voting evaluation
-        through ``tester`` (an ``evaluate.VoteTester``, whose network is reloaded from this trainer).  Keeps the best state in ``best_state`` and
+    def train_round(self, feeder, epochs, tester=None, eval_from=0.4):
+        """``Network.train`` (RandLANet.py:217-282): per epoch the feeder's batches, then the decay; from int(eval_from * epochs) on the voting
+        evaluation through ``tester`` (an ``evaluate.VoteTester``, whose network is reloaded from this trainer).  eval_from: 0.4 as S3DIS's train;
+        Semantic3D's train2 starts at 0.6 (SSRD_AL_semantic3d/RandLANet.py:310).  Keeps the best state in ``best_state`` and
         returns (best_mIoU, best_OA).  Starts from config.learning_rate (reset_lr, :213-215).
 
         With a communicator every rank's feeder holds that rank's clouds and every rank steps once per batch, so all feeders must give the same number
@@ -373,7 +374,7 @@ class Trainer:
             for batch in feeder.epoch_batches(None):
                 self.step(batch)
             self.decay(epoch)
-            if tester is not None and epoch >= int(epochs * 0.4):
+            if tester is not None and epoch >= int(epochs * eval_from):
                 self.export_to(tester.net)
                 m_iou, oa = tester.evaluate()
                 if m_iou > best_miou:
