@@ -929,6 +929,37 @@ int ssdr_draw_uniform_dev(uint64_t seed, uint32_t epoch, uint32_t step, uint32_t
 int ssdr_draw_normal_dev(uint64_t seed, uint32_t epoch, uint32_t step, uint32_t kind, uint64_t first, size_t n, double scale, double* d_out,
                          void* stream);
 
+/* ---- the radix sort under every stage, alone (csrc/radix_sort.hip) ----
+ * Stable sort of (u64 word, u32 value) pairs by bits [shift, shift + key_bits) of the word, 8 bits per pass, over nseg <= 64 independent segments of
+ * one buffer.  Every argument is handed to RadixSorter::sort_segments as it comes:
+ *   d_keys   device u64 [off[nseg]]; segment i owns the slots [off[i], off[i + 1]), off[i] a multiple of 2048, its live pairs are the first
+ *            cnt[i] = min(d_cnt[i], n_host[i]) of them (n_host[i] without d_cnt); the slots behind them are neither read nor written.  Bits at and above
+ *            shift + key_bits must be zero; what sits below `shift` travels with its word
+ *   d_vals   device u32 [off[nseg]], or NULL: keys only
+ *   off      host int32 [nseg + 1];  n_host  host int32 [nseg];  d_cnt  device int32 [nseg], or NULL
+ *   d_andor  device u64 [nseg][2], or NULL: AND and OR of every segment's words when the caller knows them (any subset of the AND's bits and superset of
+ *            the OR's will do, an empty segment gives ~0, 0); NULL: a pre-pass reads the keys.  A pass whose digit AND and OR agree on in every
+ *            segment is skipped on the device
+ *   flags    SSDR_SORT_WIDE_HIGH: RadixSorter::wide_high for this call (from 16 384 pairs on the passes above bit 32 run as wide passes, not in the
+ *            one-workgroup kernel).  SSDR_SORT_INPUT_IN_ALT: the sorter's input_in_alt protocol — the entry reserves, copies the off[nseg] slots of
+ *            d_keys / d_vals into the sorter's own buffers, fills d_keys / d_vals with the byte 0xA5 and sorts from there: the result comes home to
+ *            d_keys / d_vals, the slots no live pair lands in keep the fill.  Any other bit: SSDR_ERR_INVALID
+ * nseg <= 0 or off[nseg] <= 0: SSDR_OK, nothing is touched.  nseg > 64, an off[i] that is no multiple of 2048, off[i + 1] < off[i] + n_host[i],
+ * shift < 0 or shift + key_bits > 64: SSDR_ERR_INVALID, nothing is touched.  The sorter belongs to `stream` and to this entry alone: calls on one
+ * stream reuse it (its buffers grow), a new stream starts from nothing. */
+#define SSDR_SORT_WIDE_HIGH    1
+#define SSDR_SORT_INPUT_IN_ALT 2
+int ssdr_radix_sort_dev(uint64_t* d_keys, uint32_t* d_vals, int nseg, const int32_t* off, const int32_t* n_host, const int32_t* d_cnt, int key_bits,
+                        int shift, const uint64_t* d_andor, int flags, void* stream);
+/* Read-only view of the newest ssdr_radix_sort_dev call on `stream` (waits for the stream; changes nothing).  out8 (host): what the host decided when
+ * it launched — [0] wide passes launched (npass), [1] 1 when the passes above bit 32 were chosen wide, [2] 1 when the one-workgroup kernel for them
+ * (rs_high_passes) was launched, [3] grid of rs_hist / rs_scatter (g), [4] grid.x of the AND/OR pre-pass (gao; computed also when d_andor replaced the
+ * pre-pass), [5] the segment grid rs_finish is sized by (gseg), [6] tiles of the buffer (nb), [7] the row length of the histogram table (nblocks_max).
+ * All zero after a call that was refused or had nothing to sort, and before the first call.
+ * words_out (optional, host u64 [2 * nseg] of that call): AND and OR per segment as the kernels used them (the pre-pass's result or the caller's
+ * d_andor), copied back from the sorter; left untouched when out8 is all zero. */
+int ssdr_radix_sort_info(void* stream, int32_t* out8, uint64_t* words_out);
+
 /* ---- plain device memory for callers without their own allocator (tests, the ctypes mirror) ---------- */
 int ssdr_dev_alloc(size_t bytes, void** d_ptr);
 int ssdr_dev_free(void* d_ptr);

@@ -12,6 +12,9 @@
 // never straddles segments); its live pairs are the first cnt[s] slots, cnt[s] = min(d_cnt[s], n_host[s]) when a
 // device count is given.  Stability inside a tile: wave w owns 512 consecutive pairs and ranks them with wave-private
 // digit counters (8 ballots give every lane the mask of lanes holding the same digit), two barriers per tile.
+//
+// ssdr_radix_sort_dev (end of the file) is the sorter alone behind the C ABI, ssdr_radix_sort_info the host's launch record of its newest call:
+// tests/test_sort_paths.py reaches every branch below through them.
 #include "ssdr_internal.hpp"
 
 namespace ssdr {
@@ -265,8 +268,8 @@ __global__ __launch_bounds__(1024) void rs_high_passes(SortPtrs s) {
         int par; if (!pass_runs(s, p, par)) continue;      // uniform
         for (int sg = 0; sg < s.seg.nseg; ++sg) {
             const int n = seg_count(s, sg), so = s.seg.off[sg];
-            const uint64_t* K = s.k[par] + so; const uint32_t* V = s.v[par] + so;
-            uint64_t* KO = s.k[par ^ 1] + so; uint32_t* VO = s.v[par ^ 1] + so;
+            const uint64_t* K = s.k[par] + so; const uint32_t* V = s.kv ? s.v[par] + so : nullptr;      // keys only: one of s.v[] is null, and null takes no offset
+            uint64_t* KO = s.k[par ^ 1] + so; uint32_t* VO = s.kv ? s.v[par ^ 1] + so : nullptr;
             if (tid < 256) h[tid] = 0;
             __syncthreads();
             for (int i = tid; i < n; i += 1024) atomicAdd(&h[digit_of(s, K[i], p)], 1u);
@@ -330,9 +333,9 @@ int RadixSorter::reserve(size_t slots) {
 
 int RadixSorter::sort_segments(uint64_t* keys, uint32_t* vals, int nseg, const int* off, const int* n_host, const int* d_cnt, hipStream_t st, int key_bits, bool input_in_alt,
                                 const unsigned long long* d_andor, int shift) {
-    if (nseg <= 0) return SSDR_OK;
-    if (nseg > RADIX_MAX_SEG) { set_error("radix sort: more than %d segments", RADIX_MAX_SEG); return SSDR_ERR_INVALID; }
-    const int slots = off[nseg];
+    last = Launch{0, 0, 0, 0, 0, 0, 0, 0}; last_nseg = 0;
+    int slots = 0;
+    SSDR_TRY(check(nseg, off, n_host, key_bits, shift, &slots));
     if (slots <= 0) return SSDR_OK;
     SSDR_TRY(reserve((size_t)slots));
     SortPtrs s; s.k[0] = keys; s.k[1] = k1.as<uint64_t>(); s.v[0] = vals; s.v[1] = v1.as<uint32_t>(); s.home = 0;
@@ -340,12 +343,8 @@ int RadixSorter::sort_segments(uint64_t* keys, uint32_t* vals, int nseg, const i
     s.andor = andor.as<unsigned long long>(); s.andor_part = s.andor + 2 * RADIX_MAX_SEG; s.hist = hist.as<unsigned>(); s.tot = hist.as<unsigned>() + 256 * (size_t)nblocks_max;
     s.d_cnt = d_cnt; s.nblocks_max = nblocks_max; s.seg.nseg = nseg;
     s.shift = shift; s.kv = vals != nullptr;
-    if (shift < 0 || shift + key_bits > 64) { set_error("radix sort: key bits [%d, %d) do not fit 64", shift, shift + key_bits); return SSDR_ERR_INVALID; }
     int maxn = 0;
-    for (int i = 0; i < nseg; ++i) {
-        if (off[i] % RS_TILE || off[i + 1] < off[i] + n_host[i]) { set_error("radix sort: segment offsets must be tile-aligned and hold the segment"); return SSDR_ERR_INVALID; }
-        s.seg.off[i] = off[i]; s.seg.n_host[i] = n_host[i]; maxn = std::max(maxn, n_host[i]);
-    }
+    for (int i = 0; i < nseg; ++i) { s.seg.off[i] = off[i]; s.seg.n_host[i] = n_host[i]; maxn = std::max(maxn, n_host[i]); }
     s.seg.off[nseg] = off[nseg];
     const int nb = (slots + RS_TILE - 1) / RS_TILE;
     const int g = std::max(1, std::min(nb, ctx().num_cu * 8));
@@ -370,6 +369,20 @@ int RadixSorter::sort_segments(uint64_t* keys, uint32_t* vals, int nseg, const i
     if (key_bits > 32 && !wide_high) hipLaunchKernelGGL(rs_high_passes, dim3(1), dim3(1024), 0, st, s);   // ... one kernel for the rest
     hipLaunchKernelGGL(rs_finish, dim3(std::min(gseg, std::max(1, 2048 / nseg)), nseg), dim3(RS_BS), 0, st, s);     // usually nothing to copy: keep the (empty) launch small
     SSDR_HIP(hipGetLastError());
+    last = Launch{npass, wide_high ? 1 : 0, key_bits > 32 && !wide_high ? 1 : 0, g, gao, gseg, nb, nblocks_max}; last_nseg = nseg;
+    return SSDR_OK;
+}
+
+int RadixSorter::check(int nseg, const int* off, const int* n_host, int key_bits, int shift, int* slots) {
+    *slots = 0;
+    if (nseg <= 0) return SSDR_OK;
+    if (nseg > RADIX_MAX_SEG) { set_error("radix sort: more than %d segments", RADIX_MAX_SEG); return SSDR_ERR_INVALID; }
+    if (off[nseg] <= 0) return SSDR_OK;
+    if (shift < 0 || shift + key_bits > 64) { set_error("radix sort: key bits [%d, %d) do not fit 64", shift, shift + key_bits); return SSDR_ERR_INVALID; }
+    // (the end of the last segment too: the kernels take off[nseg] / RS_TILE tiles, a partial tile behind them would never be sorted)
+    for (int i = 0; i < nseg; ++i)
+        if (off[i] % RS_TILE || off[i + 1] % RS_TILE || off[i + 1] < off[i] + n_host[i]) { set_error("radix sort: segment offsets must be tile-aligned and hold the segment"); return SSDR_ERR_INVALID; }
+    *slots = off[nseg];
     return SSDR_OK;
 }
 
@@ -380,4 +393,51 @@ int RadixSorter::sort(uint64_t* keys, uint32_t* vals, int n_host, const int* d_n
     return sort_segments(keys, vals, 1, off, &n_host, d_n, st, key_bits, input_in_alt);
 }
 
+namespace {
+struct SortEntryState { RadixSorter sorter; };
+}  // namespace
+
 }  // namespace ssdr
+
+using namespace ssdr;
+
+extern "C" {
+
+int ssdr_radix_sort_dev(uint64_t* d_keys, uint32_t* d_vals, int nseg, const int32_t* off, const int32_t* n_host, const int32_t* d_cnt, int key_bits, int shift,
+                        const uint64_t* d_andor, int flags, void* stream) {
+    if (flags & ~(SSDR_SORT_WIDE_HIGH | SSDR_SORT_INPUT_IN_ALT)) { set_error("radix_sort: unknown flags 0x%x", flags); return SSDR_ERR_INVALID; }
+    if (nseg > 0 && (!d_keys || !off || !n_host)) { set_error("radix_sort: NULL keys, off or n_host"); return SSDR_ERR_INVALID; }
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream);
+    RadixSorter& R = per_stream<SortEntryState>(s).sorter;
+    R.wide_high = (flags & SSDR_SORT_WIDE_HIGH) != 0;
+    const bool in_alt = (flags & SSDR_SORT_INPUT_IN_ALT) != 0;
+    if (in_alt) {       // the producer's part of the protocol: reserve, write the pairs into the sorter's buffers; the caller's own are made recognisable
+        R.last = RadixSorter::Launch{0, 0, 0, 0, 0, 0, 0, 0}; R.last_nseg = 0;
+        int slots = 0;
+        SSDR_TRY(RadixSorter::check(nseg, off, n_host, key_bits, shift, &slots));
+        if (slots <= 0) return SSDR_OK;
+        SSDR_TRY(R.reserve((size_t)slots));
+        SSDR_HIP(hipMemcpyAsync(R.alt_keys(), d_keys, 8 * (size_t)slots, hipMemcpyDeviceToDevice, s));
+        SSDR_HIP(hipMemsetAsync(d_keys, 0xA5, 8 * (size_t)slots, s));
+        if (d_vals) {
+            SSDR_HIP(hipMemcpyAsync(R.alt_vals(), d_vals, 4 * (size_t)slots, hipMemcpyDeviceToDevice, s));
+            SSDR_HIP(hipMemsetAsync(d_vals, 0xA5, 4 * (size_t)slots, s));
+        }
+    }
+    return R.sort_segments(d_keys, d_vals, nseg, off, n_host, d_cnt, s, key_bits, in_alt, reinterpret_cast<const unsigned long long*>(d_andor), shift);
+}
+
+int ssdr_radix_sort_info(void* stream, int32_t* out8, uint64_t* words_out) {
+    if (!out8) { set_error("radix_sort_info: NULL output"); return SSDR_ERR_INVALID; }
+    SSDR_TRY(ensure_init());
+    hipStream_t s = pick_stream(stream);
+    RadixSorter& R = per_stream<SortEntryState>(s).sorter;
+    SSDR_HIP(hipStreamSynchronize(s));
+    const int v[8] = {R.last.npass, R.last.wide, R.last.high, R.last.g, R.last.gao, R.last.gseg, R.last.nb, R.last.nblocks_max};
+    for (int i = 0; i < 8; ++i) out8[i] = v[i];
+    if (words_out && R.last_nseg > 0 && R.andor.p) SSDR_HIP(hipMemcpy(words_out, R.andor.p, 16 * (size_t)R.last_nseg, hipMemcpyDeviceToHost));
+    return SSDR_OK;
+}
+
+}  // extern "C"

@@ -108,8 +108,14 @@ struct RadixSorter {
     DevBuf k1, v1, hist, andor;
     int nblocks_max = 0;
     bool wide_high = false;      // keys whose bits above 32 vary (a ranking by float value): wide passes up there too when the set is large, not the one-workgroup kernel
+    // what the newest sort_segments decided on the host when it launched (plain host ints, all zero when it launched nothing; ssdr_radix_sort_info):
+    // wide passes, high passes chosen wide, rs_high_passes launched, grid of rs_hist / rs_scatter, grid.x of rs_andor, the segment grid, tiles, nblocks_max
+    struct Launch { int npass, wide, high, g, gao, gseg, nb, nblocks_max; } last = {0, 0, 0, 0, 0, 0, 0, 0};
+    int last_nseg = 0;
     int reserve(size_t slots);
     static size_t scratch_bytes(size_t slots);      // what reserve(slots) asks of the device
+    // the argument checks of sort_segments, before anything is touched; *slots = 0 with SSDR_OK: nothing to sort
+    static int check(int nseg, const int* off, const int* n_host, int key_bits, int shift, int* slots);
     // key_bits: upper bound on the significant key bits when the caller knows one (skips launching higher passes)
     // input_in_alt: the caller wrote the unsorted pairs into alt_keys() / alt_vals() (valid after reserve()) instead of keys / vals;
     // with an odd number of executed digit passes the result then lands in keys / vals without the final copy

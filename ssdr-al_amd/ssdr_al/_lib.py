@@ -173,6 +173,8 @@ def lib():
         L.ssdr_predict_scan_tile_dev.argtypes = [vp, vp, sz, vp, vp, f32, vp, vp, vp, vp]
         L.ssdr_predict_parts_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
         L.ssdr_predict_scatter_dev.argtypes = [vp, sz, vp, sz, vp, sz, vp, vp, vp]
+        L.ssdr_radix_sort_dev.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, vp]
+        L.ssdr_radix_sort_info.argtypes = [vp, vp, vp]
         _lib = _libs[path] = L
     return _lib
 
