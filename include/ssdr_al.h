@@ -929,6 +929,38 @@ int ssdr_draw_uniform_dev(uint64_t seed, uint32_t epoch, uint32_t step, uint32_t
 int ssdr_draw_normal_dev(uint64_t seed, uint32_t epoch, uint32_t step, uint32_t kind, uint64_t first, size_t n, double scale, double* d_out,
                          void* stream);
 
+/* ---- the seed, random and label-all samplers (S3/sampler2.py:344-520; csrc/select_random.hip) ----
+ * ssdr_region_draw_dev: ONE iteration of RandomSampler._iteration / SeedSampler._iteration as an item list, with the draws of the chain above
+ * (epoch = round, step = iteration).  d_labeled uint8 [S] (non-zero: labelled), d_sp_cloud i32 [S] ascending, values below num_clouds.
+ *   live clouds: those with an unlabelled region, in ascending order, L of them; u(d) = the unlabelled regions of live cloud d.
+ *   k = *d_count (device int64: the clicks left, or the seeds still to place).  The k drawn elements of range(total_num) are the k smallest by
+ *     (word(e, 0) >> (32 - key_bits), e) under kind SSDR_DRAW_REGION_COUNT;  each_file_number(d) = the number of drawn e with e % L == d.
+ *   cloud d with 0 < each_file_number(d) <= u(d): its first each_file_number(d) unlabelled regions by ascending
+ *     (word(g, 0) >> (32 - key_bits), g) under kind SSDR_DRAW_REGION_PICK, g = first_region + region id, in that order;
+ *   cloud d with each_file_number(d) > u(d): all its unlabelled regions by ascending id; the shortfall adds to the seed remainder.
+ *   d_items [max_items] / *d_n_items: the clouds in live order, each cloud's picks in pick order.
+ * SSDR_REGION_ALL (AllSampler): every unlabelled region of every cloud in ascending order; d_count is not read.
+ * d_info int64 [8]: [0] live clouds, [1] k, [2] items (before the clamp to max_items), [3] the seed remainder, [4] unlabelled regions left once every
+ *   item is labelled, [5] status (1: k > total_num, nothing is drawn — np.random.choice raises; 2: more items than max_items; 4: a region's cloud is
+ *   outside the table: the region takes no part), [6], [7] zero.
+ * ssdr_seed_label_dev: _help_seed (:232-237) over the items: d_mask[p] = 1, d_label[p] = d_gt[p] for every point of every item, d_labeled[item] = 1;
+ *   d_out int64 [3]: sp_num, p_num, status (4: an item or point id outside the arrays; it is skipped).  max_region: as for ssdr_oracle_label_dev.
+ * Both only enqueue, with scratch per stream.  Refused before anything is launched: NULL pointers, S = 0, total_num = 0, key_bits outside 1 .. 32, an
+ * unknown mode (SSDR_ERR_INVALID); more than 0x3fffffff regions, elements or items (SSDR_ERR_UNSUPPORTED).  *d_count lives on the device: a count above
+ * total_num is refused there, by status bit 1 and an empty list. */
+#define SSDR_DRAW_REGION_COUNT 3
+#define SSDR_DRAW_REGION_PICK 4
+#define SSDR_REGION_RANDOM 0
+#define SSDR_REGION_ALL    1
+int ssdr_region_draw_dev(uint64_t seed, uint32_t round, uint32_t iteration, int mode, int key_bits, uint64_t first_region, const uint8_t* d_labeled,
+                         const int32_t* d_sp_cloud, size_t S, size_t num_clouds, size_t total_num, const int64_t* d_count, int32_t* d_items, size_t max_items,
+                         int32_t* d_n_items, int64_t* d_info, void* stream);
+/* Read-only view of the newest ssdr_region_draw_dev call on `stream` (waits for the stream): out (host) [n] = each_file_number of the first n live clouds,
+ * n at most that call's num_clouds (SSDR_ERR_INVALID beyond, and before the first call). */
+int ssdr_region_draw_shares(void* stream, int32_t* out, size_t n);
+int ssdr_seed_label_dev(const int32_t* d_gt, size_t n, const int32_t* d_sp_off, const int32_t* d_sp_pts, size_t S, const int32_t* d_items, const int32_t* d_n_items,
+                        size_t max_items, size_t max_region, float* d_mask, float* d_label, uint8_t* d_labeled, int64_t* d_out, void* stream);
+
 /* ---- the radix sort under every stage, alone (csrc/radix_sort.hip) ----
  * Stable sort of (u64 word, u32 value) pairs by bits [shift, shift + key_bits) of the word, 8 bits per pass, over nseg <= 64 independent segments of
  * one buffer.  Every argument is handed to RadixSorter::sort_segments as it comes:

@@ -10,35 +10,13 @@
 // in 128 rounds of 64 segments): the tile's rank inside its segment sits above the key bits, so the segment comes out tile by tile, every tile
 // by key, ties by row, at the price of ceil(log2(tiles) / 8) more passes.
 #include "ssdr_internal.hpp"
-#include "mix32.hpp"
+#include "draw_word.hpp"
 #include <cmath>
 
 namespace ssdr {
 namespace {
 
-constexpr uint32_t LANE0 = 0x9e3779b9u, LANE1 = 0x85ebca6bu;
-
-// the part of the chain that is the same for every element of a call
-struct DrawBase { uint32_t s0, s1; };
-inline DrawBase draw_base(uint64_t seed, uint32_t epoch, uint32_t step, uint32_t kind) {
-    DrawBase b;
-    uint32_t* out[2] = {&b.s0, &b.s1};
-    const uint32_t lane[2] = {LANE0, LANE1};
-    for (int l = 0; l < 2; ++l) {
-        uint32_t s = mix32((uint32_t)seed ^ lane[l]);
-        s = mix32(s ^ (uint32_t)(seed >> 32)); s = mix32(s ^ epoch); s = mix32(s ^ step); s = mix32(s ^ kind);
-        *out[l] = s;
-    }
-    return b;
-}
-// word j of element e: two chains that differ in their first constant, added and mixed once more (one chain alone is a bijection of the low
-// word of e: the keys of a tile would be one fixed bijection of an aligned block of integers)
-__device__ __forceinline__ uint32_t draw_word(DrawBase b, uint64_t e, uint32_t j) {
-    const uint32_t lo = (uint32_t)e, hi = (uint32_t)(e >> 32);
-    uint32_t a = mix32(b.s0 ^ lo); a = mix32(a + hi); a = mix32(a ^ j);
-    uint32_t c = mix32(b.s1 ^ lo); c = mix32(c + hi); c = mix32(c ^ j);
-    return mix32(a + c);
-}
+// (DrawBase, draw_base and draw_word: draw_word.hpp)
 // 53 hashed bits from words j and j + 1: the upper 27 of the first above the upper 26 of the second
 __device__ __forceinline__ uint64_t draw_bits53(DrawBase b, uint64_t e, uint32_t j) {
     return ((uint64_t)(draw_word(b, e, j) >> 5) << 26) | (uint64_t)(draw_word(b, e, j + 1) >> 6);

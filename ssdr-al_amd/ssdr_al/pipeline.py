@@ -47,7 +47,8 @@ class _Pairs:
         return repr(self.tolist())
 
 
-SELECTORS = ("fps", "kcenter", "edcd", "topk", "coregcn")
+SELECTORS = ("fps", "kcenter", "edcd", "topk", "coregcn", "random", "all")
+REGION_SAMPLERS = ("random", "all")      # no scoring, no network outputs: RandomSampler / AllSampler (sampler2.py:410-520)
 
 # The words of the selection chains' int32 result buffers that the host reads.  include/ssdr_al.h defines them: d_result in the comment above
 # ssdr_gcn_fps_sampling_dev (the edcd and topk chains share its header), d_plan in the one above ssdr_gcn_fps_sharded_local_dev.
@@ -130,7 +131,8 @@ def selector_for(sampler_args, trained_gcn=False):
 class HotPath:
     def __init__(self, weights, config=ConfigS3DIS, sampler_args=("sb", "WetSU", "clsbal", "gcn_fps"), gcn_number=1, gcn_top=0,
                  select_per_tile=37, labeled_per_tile=15, seed=0, precision="f32", selector="fps", tiles32=True, min_size=1, round_num=5,
-                 label_seed=None, batch_size=None, max_size=None, chamfer_mode="f64", gcn_steps=20000, gcn_dropout=0.3, gcn_seed=0, gcn_form="auto"):
+                 label_seed=None, batch_size=None, max_size=None, chamfer_mode="f64", gcn_steps=20000, gcn_dropout=0.3, gcn_seed=0, gcn_form="auto",
+                 draws="device", draw_seed=0, max_iter=32, total_num=None, draw_key_bits=32):
         self.cfg = config
         self.net = None if weights is None else randlanet.Network(config).load(weights).set_precision(precision).set_formulation(tiles32)
         self.sampler_args = list(sampler_args)
@@ -157,6 +159,17 @@ class HotPath:
         assert selector in SELECTORS, "selector must be one of %s" % (SELECTORS,)
         self.selector = selector
         self.gcn_steps, self.gcn_dropout, self.gcn_seed, self.gcn_form = int(gcn_steps), float(gcn_dropout), int(gcn_seed), gcn_form
+        # "random" / "all": RandomSampler / AllSampler (sampler2.py:455-520, :410-453) — no scoring; SeedSampler is seed_round().  draws: "device" (counter-based,
+        # a function of (draw_seed, round_num, iteration); csrc/select_random.hip) or "host" (draw_rng, a np.random.RandomState consumed as the reference
+        # consumes np.random); max_iter: where the loop stops when only regions below min_size are left; total_num: the samplers' total_num (default: S)
+        assert draws in ("device", "host"), 'draws must be "device" or "host"'
+        self.draws, self.draw_seed, self.max_iter, self.draw_key_bits = draws, int(draw_seed), int(max_iter), int(draw_key_bits)
+        self.total_num = None if total_num is None else int(total_num)
+        self.draw_rng = np.random.RandomState(self.draw_seed & 0xffffffff) if draws == "host" else None
+        self._unl_lists = None      # draws="host": every cloud's unlabelled list in the reference's order (local ids), kept across rounds
+        self._pred_resident = False # predicted classes (self.cls) are those of a prediction pass over the resident outputs
+        self.record_shares = False  # device draws: read every iteration's each_file_number back too (LabelResult.draw_info; the tests)
+        self._drawn0 = None         # iteration 0 of a "random" / "all" round, drawn by step_selection()
         self.fps_start = 0          # np.random.randint(0, n) in the reference (fps_gcn_cpu.py:133); fixed here
         self.stream = None          # stream of the pyramid .. scoring stages (None = the library's main stream)
         self.front_stream = None    # stream of the front end (grid-subsample + tiles)
@@ -320,6 +333,8 @@ class HotPath:
         """scoring + selection over the resident network outputs (from_clouds); comm: the sharded run's exchanges"""
         if comm is not None and self.selector == "coregcn":
             raise ValueError('selector="coregcn" with a communicator: the sharded form of the trained-GCN selector is not offered')
+        if self.selector in REGION_SAMPLERS:
+            return self._region_select(comm)
         self._score_async(comm)
         return self._select(comm)
 
@@ -351,6 +366,7 @@ class HotPath:
         """labeled[b] = the (global) ids of cloud b's regions that are already labelled (what total_obj["unlabeled"] no longer lists)"""
         cfg = self.cfg
         self._dist = None; self.global_order = None      # a sharded run's static tables (labelled mask, populations, the global draw) belong to the labelling
+        self._unl_lists = self._drawn0 = None            # ... and so do the host draws' unlabelled lists and a drawn, not yet labelled iteration
         self.labeled = labeled
         self.labeled_mask = np.zeros(self.S, bool)
         for b in self.labeled:
@@ -520,6 +536,7 @@ class HotPath:
         all-reduce of the class histogram, all-gather of the (masked, padded) region uncertainties, then the global ranking."""
         cfg, L = self.cfg, _lib.lib()
         n = self.n_pts
+        self._pred_resident = True
         um = {"lc": 0, "entropy": 1, "sb": 2}[[a for a in self.sampler_args if a in ("lc", "entropy", "sb")][0]]
         rm = {"mean": 0, "sum_weight": 1, "WetSU": 2}[[a for a in self.sampler_args if a in ("mean", "sum_weight", "WetSU")][0]]
         st = self.score_stream if self.score_stream is not None else self.stream
@@ -976,6 +993,8 @@ class HotPath:
         comm: the communicator of the last selection (a sharded round): every rank judges its own picks, the verdict records are all-gathered on the
         selection stream, every rank runs the same walk over all of them and applies its own.  The counters, budget_left and the class list are then
         global and equal on all ranks; `used` / `walk_pos` are this rank's used picks and their positions in the global walk."""
+        if self.selector in REGION_SAMPLERS:
+            return self._region_label(mode, threshold, min_size, budget, comm)
         last = None if self._collected is None else self._collected.comm
         if last is not None and comm is None:
             raise ValueError("label_selected: the last selection ran with a communicator; the budget walk is global over all ranks' picks: pass that "
@@ -1098,6 +1117,181 @@ class HotPath:
         slots = slots[np.argsort(pos[slots], kind="stable")]      # this rank's used picks in the order the global walk met them
         return self._label_end(out, d_cls, d_labeled, own[slots], pos[slots].astype(np.int64))
 
+    # ---- the seed, random and label-all rounds (sampler2.py:344-520): no scoring, no network outputs ----------------
+    def _region_refuse_comm(self, comm):
+        if comm is not None:
+            raise ValueError('selector="%s" with a communicator: the sharded form of the seed / random / label-all samplers is not offered' % self.selector)
+
+    def _unl_host(self):
+        """draws="host": every cloud's unlabelled list (ids inside the cloud) as total_obj["unlabeled"] holds it; ascending when first made"""
+        if self._unl_lists is None:
+            base = np.concatenate([np.asarray(self.sp_base, np.int64), [self.S]])
+            lists = {}
+            for b in range(self.B):
+                ids = np.flatnonzero(~self.labeled_mask[base[b]:base[b + 1]]).tolist()
+                if ids:
+                    lists[b] = ids
+            self._unl_lists = lists
+        return self._unl_lists
+
+    @property
+    def unlabeled_lists(self):
+        """total_obj["unlabeled"] as the seed / random / label-all rounds keep it: {cloud: [region id inside the cloud, ...]}, live clouds only; with
+        draws="host" in the reference's own order, otherwise ascending"""
+        return self._unl_host()
+
+    def _region_begin(self):
+        """the device state one seed / random / label-all round keeps across its iterations"""
+        st = self.sel_stream
+        if self.S == 0:
+            raise ValueError("the seed / random / label-all samplers need at least one region")
+        if self.pseudo_mask is None:
+            self.set_pseudo_gt(np.zeros((2, self.n_pts), np.float32))
+        return dict(d_labeled=DevArray.from_host(self.labeled_mask.astype(np.uint8), st), d_items=DevArray((self.S,), np.int32), d_n=DevArray((1,), np.int32),
+                    d_info=DevArray((8,), np.int64), d_budget=DevArray((1,), np.int64), labeled=self.labeled_mask.copy(), it=0, drawn=[], infos=[], picks=None, items=None)
+
+    def _region_draw(self, R, click, mode, round_num):
+        """One iteration's item list into R["d_items"] / R["d_n"]: `click` elements of range(total_num) shared among the live clouds, every cloud's picks
+        (mode REGION_RANDOM), or every unlabelled region (REGION_ALL).  *R["d_budget"] holds `click`.  -> (items as global region ids, info)"""
+        L, st = _lib.lib(), self.sel_stream
+        T = self.S if self.total_num is None else self.total_num
+        if mode == sampler.REGION_RANDOM and click > T:
+            raise ValueError("Cannot take a larger sample than population when 'replace=False' (%d clicks of total_num = %d)" % (click, T))
+        if self.draws == "host":
+            unl = self._unl_host()
+            if mode == sampler.REGION_ALL:
+                picks, each, remain = [(c, list(unl[c])) for c in unl], np.array([len(unl[c]) for c in unl], np.int32), 0
+            else:
+                picks, each, remain = sampler.seed_iteration_host(T, unl, click, self.draw_rng)
+            items = np.array([self.sp_base[c] + s for c, sps in picks for s in sps], np.int64)
+            if len(items):
+                _lib.check(L.ssdr_memcpy_h2d_on(R["d_items"].ptr, _lib.ptr(np.ascontiguousarray(items, np.int32)), 4 * len(items), st))
+            _lib.check(L.ssdr_memcpy_h2d_on(R["d_n"].ptr, _lib.ptr(np.array([len(items)], np.int32)), 4, st))
+            info = dict(live=len(each), k=int(click), items=len(items), remain=int(remain), each=np.asarray(each, np.int64))
+            R["picks"] = picks
+        else:
+            _lib.check(L.ssdr_region_draw_dev(self.draw_seed & 0xffffffffffffffff, int(round_num) & 0xffffffff, R["it"], mode, self.draw_key_bits, 0, R["d_labeled"].ptr,
+                                              self.d_sp_cloud.ptr, self.S, max(self.B, 1), T, R["d_budget"].ptr, R["d_items"].ptr, self.S, R["d_n"].ptr, R["d_info"].ptr, st))
+            w = R["d_info"].to_host(st)                           # waits for the selection stream alone
+            sampler.region_draw_status_check(int(w[5]), int(w[1]), T)
+            items = R["d_items"].to_host(st)[: int(w[2])].astype(np.int64)
+            info = dict(live=int(w[0]), k=int(w[1]), items=int(w[2]), remain=int(w[3]), each=None)
+            if self.record_shares:
+                info["each"] = np.zeros(info["live"], np.int32)
+                _lib.check(L.ssdr_region_draw_shares(st, _lib.ptr(info["each"]), info["live"]))
+        R["items"], R["info"] = items, info
+        R["drawn"].append(items); R["infos"].append(info)
+        return items, info
+
+    def _region_set_budget(self, R, click):
+        _lib.check(_lib.lib().ssdr_memcpy_h2d_on(R["d_budget"].ptr, _lib.ptr(np.array([int(click)], np.int64)), 8, self.sel_stream))
+
+    def _region_select(self, comm=None):
+        """step_selection() of "random" / "all": iteration 0's picks for the round's batch_size clicks — (arange, the picks as (cloud, region))"""
+        self._region_refuse_comm(comm)
+        R = self._region_begin()
+        R["click0"] = int(self._sel_static["batch"])
+        self._region_set_budget(R, R["click0"])
+        items, _ = self._region_draw(R, R["click0"], sampler.REGION_ALL if self.selector == "all" else sampler.REGION_RANDOM, self.round_num)
+        self._drawn0, self._last_sel = R, None
+        self._selected = _Pairs(*self._room_sp(items))
+        return np.arange(len(items), dtype=np.int32), _Pairs(self.sp_cloud_h[items], items)
+
+    def _region_label(self, mode, threshold, min_size, budget, comm):
+        """label_selected() of "random" / "all": the walk over iteration 0's items, then (random) further draws and walks while clicks and unlabelled
+        regions last — RandomSampler._iteration's recursion (sampler2.py:463-493) as a loop that max_iter ends"""
+        self._region_refuse_comm(comm)
+        R = self._drawn0
+        if R is None:
+            raise RuntimeError("label_selected: no selection to label (run step_selection() first)")
+        m = sampler.label_mode([mode] if isinstance(mode, str) else mode)
+        if m == 1 and not self._pred_resident:
+            raise ValueError('label_selected: mode="NAIL" with selector="%s" needs predicted classes resident from an earlier prediction pass (the reference '
+                             'passes prob_class=None and fails on the first impure region); "dominant" always works' % self.selector)
+        rand = self.selector == "random"
+        if budget is not None and int(budget) != R["click0"]:
+            if rand:
+                raise ValueError("label_selected: iteration 0 was drawn for batch_size = %d clicks; a round of %d clicks needs HotPath(batch_size=%d)" % (R["click0"], int(budget), int(budget)))
+            R["click0"] = int(budget)                             # (label-all draws nothing: any budget walks the same list)
+            self._region_set_budget(R, R["click0"])
+        min_size = (self.min_size if min_size is None else int(min_size)) if rand else 1      # AllSampler passes min_size=1 (sampler2.py:449)
+        L, st, nc = _lib.lib(), self.sel_stream, int(self.cfg.num_classes)
+        max_region = int(self.sp_size_h.max()) if self.S else 1
+        click, status = R["click0"], 0
+        counters, entries, used_ids, forms = np.zeros(6, np.int64), [], [], np.zeros(2, np.int64)
+        while True:
+            items, M = R["items"], len(R["items"])
+            cap = max(1, min(M * nc, max(click, 0) + nc + 1))
+            d_used, d_proc = DevArray((max(M, 1),), np.uint8), DevArray((max(M, 1),), np.int32)
+            d_cls, d_out = DevArray((cap,), np.int32), DevArray((12,), np.int64)
+            _lib.check(L.ssdr_oracle_label_dev(self.tile_l.ptr, self.cls.ptr, self.n_pts, self.sp_off.ptr, self.sp_pts.ptr, self.S, self.d_sp_cloud.ptr, max(self.B, 1),
+                                               R["d_items"].ptr, R["d_n"].ptr, M, None, max_region, max(nc, 1), nc, m, float(threshold), min_size, R["d_budget"].ptr,
+                                               self.pseudo_mask.ptr, self.pseudo_label.ptr, d_used.ptr, R["d_labeled"].ptr, d_cls.ptr, cap, d_proc.ptr, d_out.ptr, st))
+            out = d_out.to_host(st)                              # the budget and the counters: one read per iteration
+            sampler.label_status_check(int(out[8]))
+            used_f, proc = d_used.to_host(st)[:M], d_proc.to_host(st)[:M]
+            used = items[proc[used_f[proc] != 0]] if M else items
+            self._region_spent(R, used)
+            counters += out[:6]; forms += out[10:12]; entries.append(d_cls.to_host(st)[: int(out[6])]); used_ids.append(used)
+            click = int(out[7])
+            R["it"] += 1
+            if not rand or click <= 0 or R["labeled"].all():
+                break
+            if R["it"] >= self.max_iter:                         # only regions below min_size are left: the reference recurses for ever
+                status |= sampler.ST_MAX_ITER
+                break
+            self._region_draw(R, click, sampler.REGION_RANDOM, self.round_num)
+        return self._region_end(R, counters, click, np.concatenate(used_ids), np.concatenate(entries), dict(wave=int(forms[0]), block=int(forms[1])), status)
+
+    def _region_spent(self, R, used):
+        """what _help / _help_seed do to the unlabelled lists once a walk has used `used` (global ids) of the iteration's items"""
+        R["labeled"][used] = True
+        if self.draws == "host":
+            gone = set(int(x) for x in used)
+            for c, sps in R["picks"]:
+                sampler.remove_used(self._unl_lists, c, [s for s in sps if self.sp_base[c] + s in gone])
+
+    def _region_end(self, R, counters, budget_left, used_ids, entries, forms, status):
+        st = self.sel_stream
+        self._class_list_h = np.concatenate([self._class_list_h, entries]).astype(np.int32)
+        self.selected_class_list = DevArray.from_host(self._class_list_h)
+        mask = R["d_labeled"].to_host(st)[: self.S] != 0
+        lists = self._unl_lists
+        ids = np.flatnonzero(mask)                               # (ascending, and so are the clouds: one cut per cloud)
+        parts = np.split(ids, np.searchsorted(ids, np.asarray(self.sp_base[1:], np.int64)))
+        self.set_labeled({b: set(parts[b].tolist()) for b in range(self.B)})
+        self._unl_lists = lists if self.draws == "host" else None      # (set_labeled drops them: these ARE the lists behind the new mask)
+        return LabelResult(self, dict(zip(sampler.LABEL_COUNTERS, (int(x) for x in counters))), int(budget_left), _Pairs(*self._room_sp(np.asarray(used_ids, np.int64))),
+                           np.asarray(entries, np.int32), forms, None, iterations=R["it"], drawn=R["drawn"], status=status, draw_info=R["infos"])
+
+    def seed_round(self, number, round_num=0):
+        """SeedSampler.sampling (sampler2.py:344-408): `number` regions drawn among the clouds and labelled PRECISELY (every point its own ground truth,
+        no budget, no min_size, no class entries); a cloud smaller than its share is taken whole and the shortfall is drawn again, until none is left.
+        Returns a LabelResult: counters sp_num / p_num, budget_left = the remainder that could not be placed."""
+        L, st = _lib.lib(), self.sel_stream
+        R = self._region_begin()
+        remain, status = int(number), 0
+        sp_num = p_num = 0
+        max_region = int(self.sp_size_h.max()) if self.S else 1
+        d_out = DevArray((3,), np.int64)
+        while remain > 0 and not R["labeled"].all():
+            if R["it"] >= self.max_iter:
+                status |= sampler.ST_MAX_ITER
+                break
+            self._region_set_budget(R, remain)
+            items, info = self._region_draw(R, remain, sampler.REGION_RANDOM, round_num)
+            _lib.check(L.ssdr_seed_label_dev(self.tile_l.ptr, self.n_pts, self.sp_off.ptr, self.sp_pts.ptr, self.S, R["d_items"].ptr, R["d_n"].ptr, len(items), max_region,
+                                             self.pseudo_mask.ptr, self.pseudo_label.ptr, R["d_labeled"].ptr, d_out.ptr, st))
+            out = d_out.to_host(st)
+            sampler.label_status_check(int(out[2]))
+            sp_num += int(out[0]); p_num += int(out[1])
+            self._region_spent(R, items)
+            remain = info["remain"]
+            R["it"] += 1
+        counters = np.array([sp_num, p_num, 0, 0, 0, 0], np.int64)
+        used = np.concatenate(R["drawn"]) if R["drawn"] else np.zeros(0, np.int64)
+        return self._region_end(R, counters, remain, used, np.zeros(0, np.int32), dict(wave=0, block=0), status)
+
     def step(self, comm=None, timed_stages=False):
         """One pass of the hot path over the loaded batch of rooms.  Returns the selected candidate indices."""
         t = [time.perf_counter()]
@@ -1125,12 +1319,16 @@ class LabelResult:
     """What HotPath.label_selected / ALRound.label hand back: `mask` / `label` (device, float32 [n]: the two rows of pseudo_gt over all points, the
     HotPath's own resident arrays), `used` as (room id, superpoint in room) pairs in the order the walk met them, the six `counters` of the
     reference's `w`, `budget_left` (may be negative), `class_entries` appended to selected_class_list, `forms`: regions judged per kernel form,
-    `walk_pos`: the position of every entry of `used` in the walk.  After a sharded labelling the counters, budget_left, class_entries and forms are
+    `walk_pos`: the position of every entry of `used` in the walk, `iterations` / `drawn` / `status`: the draw iterations of a seed, random or
+    label-all round, their items and why the loop stopped (budget_left is the seed round's remainder).  After a sharded labelling the counters, budget_left, class_entries and forms are
     global (equal on all ranks), `used` / `walk_pos` this rank's share of the global walk."""
-    def __init__(self, hp, counters, budget_left, used, class_entries, forms, walk_pos=None):
+    def __init__(self, hp, counters, budget_left, used, class_entries, forms, walk_pos=None, iterations=1, drawn=None, status=0, draw_info=None):
         self._hp, self.mask, self.label = hp, hp.pseudo_mask, hp.pseudo_label
         self.counters, self.budget_left, self._used, self.class_entries, self.forms = counters, budget_left, used, class_entries, forms
         self.walk_pos = walk_pos
+        # the seed / random / label-all rounds: iterations run, the items of every iteration (region ids), sampler.ST_MAX_ITER when max_iter stopped the loop
+        # draw_info: per iteration dict(live, k, items, remain, each) — the live clouds, the clicks drawn for, the items, the seed remainder, each_file_number
+        self.iterations, self.drawn, self.status, self.draw_info = int(iterations), drawn, int(status), draw_info
 
     @property
     def used(self):
@@ -1178,13 +1376,17 @@ class ALRound:
     SLOTS = 4          # batches in flight = HIP streams = the runtime's hardware queues (2: 54.9 ms for 17 batches, 3: 52.2, 4: 49.1, 5: 56.9, 6: 49.4, 8: 49.6; a stream per STAGE: 60-64)
 
     def __init__(self, weights, rooms, n_batches, config=ConfigS3DIS, batch_size=10000, round_num=5, labeled_per_tile=15, precision="f32",
-                 selector="fps", tiles32=True, seed=0, gcn_number=1, gcn_top=0, min_size=1, gcn_steps=20000, gcn_dropout=0.3, gcn_seed=0, gcn_form="auto", comm=None):
+                 selector="fps", tiles32=True, seed=0, gcn_number=1, gcn_top=0, min_size=1, gcn_steps=20000, gcn_dropout=0.3, gcn_seed=0, gcn_form="auto", comm=None,
+                 draws="device", draw_seed=0, max_iter=32):
         L = _lib.lib()
         self.comm = comm
+        draw_kw = dict(draws=draws, draw_seed=draw_seed, max_iter=max_iter)      # the seed / random / label-all samplers' draws (HotPath)
         self.batch_ids = list(range(int(n_batches)))          # the global ids of this process's batches
         if comm is not None:
             if selector == "coregcn":
                 raise ValueError('selector="coregcn" with a communicator: the sharded form of the trained-GCN selector is not offered')
+            if selector in REGION_SAMPLERS:
+                raise ValueError('selector="%s" with a communicator: the sharded form of the seed / random / label-all samplers is not offered' % selector)
             if comm.world > int(n_batches):                   # (raised on every rank: nobody is left waiting in an exchange)
                 raise ValueError("ALRound: %d batches cannot be shared among %d ranks (a rank would own none)" % (int(n_batches), comm.world))
             self.batch_ids = [int(b) for b in np.array_split(np.arange(int(n_batches)), comm.world)[comm.rank]]
@@ -1239,7 +1441,7 @@ class ALRound:
         sel_list = np.random.default_rng([seed, 999983]).integers(0, config.num_classes, 4000)
         self.sel = HotPath.from_device(self.xyz, self.probs, self.f32, self.tile_l, np.concatenate(offs), np.concatenate(pts), np.concatenate(cloud), labeled, sel_list,
                                        config, room_ids=tile_ids, batch_size=batch_size, round_num=round_num, selector=selector, gcn_number=gcn_number, gcn_top=gcn_top, min_size=min_size, seed=seed,
-                                       gcn_steps=gcn_steps, gcn_dropout=gcn_dropout, gcn_seed=gcn_seed, gcn_form=gcn_form)
+                                       gcn_steps=gcn_steps, gcn_dropout=gcn_dropout, gcn_seed=gcn_seed, gcn_form=gcn_form, **draw_kw)
         self.sel.stream = self.sel.score_stream = self.sel.sel_stream = s_i
         self.sel.front_stream = s_i; self.sel.pipelined = True
         self.sel.pt_off = np.arange(self.tiles + 1, dtype=np.int64) * N
@@ -1290,6 +1492,8 @@ class ALRound:
 
     def run(self):
         """the whole round; returns (picked candidate indices, candidate list) as HotPath.step does"""
+        if self.sel.selector in REGION_SAMPLERS:      # RandomSampler / AllSampler look at no network output: no inference, no scoring
+            return self.sel.step_selection(self.comm)
         self.infer_all()
         self.sel._score_async(self.comm)
         self.sel._select_issue(self.comm)
@@ -1304,6 +1508,12 @@ class ALRound:
         """the oracle over the round's picks (HotPath.label_selected on the round's arrays): the labelled set, the class list and the pseudo labels
         are then those of the next round"""
         return self.sel.label_selected(mode=mode, threshold=threshold, min_size=min_size, budget=budget, comm=self.comm)
+
+    def seed(self, number, round_num=0):
+        """SeedSampler over the round's regions (HotPath.seed_round): the labelled set every experiment starts from, in place of the labelled stand-in"""
+        if self.comm is not None:
+            raise ValueError("ALRound.seed with a communicator: the sharded form of the seed / random / label-all samplers is not offered")
+        return self.sel.seed_round(number, round_num)
 
 
 class BatchStreams:

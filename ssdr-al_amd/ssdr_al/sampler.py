@@ -120,6 +120,62 @@ def oracle_labeling(superpoint_inds, components, input_gt, pseudo_gt, cloud_name
     return pseudo_gt, [superpoint_inds[i] for i in np.flatnonzero(used)]
 
 
+# ---- the seed, random and label-all samplers (sampler2.py:344-520): csrc/select_random.hip ------------------------------------------------------
+REGION_RANDOM, REGION_ALL = 0, 1
+DRAW_ST_COUNT, DRAW_ST_ITEMS, DRAW_ST_CLOUD = 1, 2, 4
+ST_MAX_ITER = 256          # LabelResult.status: the loop stopped after max_iter iterations (the reference recurses for ever there)
+
+
+def _iteration_draws(total_num, unlabeled, number, random_state):
+    """The draws of one SeedSampler._iteration / RandomSampler._iteration (sampler2.py:357-379, :465-486), consuming `random_state` exactly as the
+    reference consumes np.random: unlabeled = {cloud: [region, ...]} in the reference's dict and list order.
+    -> ([(cloud, [region, ...])] in the order _help is called, each_file_number, the seed remainder)"""
+    rand_inds = random_state.choice(np.arange(int(total_num)), int(number), replace=False)
+    names = list(unlabeled)
+    length = len(names)
+    each_file_number = np.zeros([length], dtype=np.int32)
+    for ind in rand_inds:
+        each_file_number[ind % length] += 1
+    picks, remain = [], 0
+    for i in range(length):
+        if each_file_number[i] > 0:
+            unl = unlabeled[names[i]]
+            if len(unl) >= each_file_number[i]:
+                inds = random_state.choice(list(unl), int(each_file_number[i]), replace=False).tolist()
+            else:
+                inds = list(unl)
+                remain += int(each_file_number[i]) - len(inds)
+            picks.append((names[i], inds))
+    return picks, each_file_number, remain
+
+
+def random_iteration_host(total_num, unlabeled, click, random_state):
+    """RandomSampler._iteration's draws for budget["click"] = click -> (picks, each_file_number)"""
+    picks, each, _ = _iteration_draws(total_num, unlabeled, click, random_state)
+    return picks, each
+
+
+def seed_iteration_host(total_num, unlabeled, number, random_state):
+    """SeedSampler._iteration's draws -> (picks, each_file_number, remain_number)"""
+    return _iteration_draws(total_num, unlabeled, number, random_state)
+
+
+def remove_used(unlabeled, cloud, used):
+    """what _help / _help_seed leave of a cloud's list (sampler2.py:214-216), that expression's order included"""
+    unlabeled[cloud] = list(set(unlabeled[cloud]) - set(used))
+    if len(unlabeled[cloud]) == 0:
+        del unlabeled[cloud]
+
+
+def region_draw_status_check(status, k=None, total_num=None):
+    if status & DRAW_ST_COUNT:
+        raise ValueError("Cannot take a larger sample than population when 'replace=False' (%s clicks of total_num = %s)" % (k, total_num))
+    if status & DRAW_ST_ITEMS:
+        raise RuntimeError("region_draw: more items than the item list holds")
+    if status & DRAW_ST_CLOUD:
+        raise ValueError("region_draw: a region's cloud is outside the cloud table")
+
+
 def add_clsbal(class_num, region_class, region_uncertainty, total_obj, skip=None):
     """sampler2.py:262-266.  The reference passes the UNLABELLED regions only (prediction(), :612-627); a caller that keeps every region in
     one array marks the others in `skip` (non-zero: not part of the population)."""
