@@ -215,8 +215,7 @@ int ssdr_tile_from_rooms_batch_dev(const float* d_points, const float* d_feature
 int ssdr_tile_from_rooms_stats(void* stream, int32_t* out_stage, int32_t* out_reduced, int32_t* out_buckets, size_t num_clouds);
 /* Per cloud of the last ssdr_tile_from_rooms_batch_dev on `stream` (waits for it; int64 [num_clouds] each, may be NULL): the 32-byte records its partition wrote
  * and the cloud's points.  The partition writes only the records of the buckets a stage reduces: records < points for a cloud whose first stage sufficed with a
- * part of its buckets, records == points for a cloud that went on to a later stage or was reduced whole.  -1 / -1 when the call took the sort; records -1 under
- * SSDR_FE_SCATTER_PRUNE=0 (development: the one scatter of every record, which does not count).  A planned call whose plan holds the records (below) writes
+ * part of its buckets, records == points for a cloud that went on to a later stage or was reduced whole.  -1 / -1 when the call took the sort.  A planned call whose plan holds the records (below) writes
  * none: for it the first number is "records the stages were given", not "records written" — the points of the buckets the first stage was handed, plus, for a
  * cloud that went on, the points of all its other buckets — which is the number the unplanned call reports for the same inputs. */
 int ssdr_tile_from_rooms_scatter_stats(void* stream, int64_t* out_scattered, int64_t* out_points, size_t num_clouds);

@@ -16,14 +16,14 @@
 //                     work item per non-empty bucket
 //   scatter           second read of the points: 32-byte records (xyz, index in the cloud | features, labels) written behind LDS cursors,
 //                     a bucket's records contiguous (order inside a bucket is whatever the LDS atomics give: the index travels)
-//   reduce            one workgroup per bucket: records -> LDS, LDS histogram over the bucket's <= 1024 voxels, every voxel's members
-//                     ranked by their index (input order), sequential sums, label vote; the bucket's rows (32 bytes: row + voxel id) go
-//                     back over the bucket's own records, with its occupancy per local row (y, z)
+//   reduce            one workgroup per bucket: LDS histogram over the bucket's <= 1024 voxels from the first half of every record, every voxel's members
+//                     ranked by their index (input order), then the records read in place in that order (the workgroup has just streamed them: L2) for the
+//                     sequential sums and the label vote; the bucket's rows (32 bytes: row + voxel id) go to the rows region, with its occupancy per local row (y, z)
 //   rowpre / rowscan  number of occupied voxels in front of every (row, bucket) in key order (key = ix + nx (iy + ny iz): rows of x)
 //   move              every bucket's rows to their final position
 //
-// HBM traffic: 12 N (minmax) + 12 N (count) + 28 N + 32 N (scatter) + 32 N + 32 M (reduce) + 32 M + 28 M (move) bytes for N points and M
-// voxels, against 28 (N + M) algorithmic.  The staged reduction of ssdr_tile_from_rooms_batch_dev (below) orders a room's buckets BEFORE the scatter and writes and
+// HBM traffic: 12 N (minmax) + 12 N (count) + 28 N + 32 N (scatter) + 32 N + 32 M (reduce: every record once from HBM, its second reading from the L2; the rows) + 32 M + 28 M
+// (move) bytes for N points and M voxels, against 28 (N + M) algorithmic.  The staged reduction of ssdr_tile_from_rooms_batch_dev (below) orders a room's buckets BEFORE the scatter and writes and
 // reduces only the share p of the points that lies in stage 1's buckets: 12 N + 12 N + 28 N + 32 p N (scatter) + 32 p N + 32 p M (reduce) + (32 + 28) p M (move);
 // p = 0.42 on the bench's rooms.  A room that goes on to stage 2 pays 28 N more (a second read of its points) for the other 32 (1 - p) N of records.  A call with a room
 // plan (FePlan) starts at the order: the 12 N + 12 N of minmax and count were paid once, when the plan was built — and so were the scatter's 28 N + 32 N when the plan holds the
@@ -33,6 +33,7 @@
 #include "block_prims.hpp"
 #include "voxel_label.hpp"
 #include "subsample_types.hpp"
+#include "frontend.hpp"
 #include <memory>
 
 namespace ssdr {
@@ -44,21 +45,13 @@ constexpr int FE_NT = 1024;          // their workgroup size
 constexpr int FE_PPT = 12, FE_SNT = 1024;      // points per thread and step of the scatter, its workgroup size: 12288 points per step leave ~12 records = three
                                               // whole lines in a bucket at a time, and one workgroup per CU halves the lines the L2 has open (PPT 4: 0.51 ms, 8: 0.44, 12: 0.36;
                                               // 512 threads x 24 the same, x 32 = the whole chunk in one step spills: 0.37)
-#ifndef FE_PAIR_STORES
-#define FE_PAIR_STORES 1
-#endif
 constexpr int FE_LR = 64;            // local rows (y, z) of a bucket: 8 x 8
 constexpr int FE_VMAX = 1024;        // voxels per bucket (sx <= 4)
-#ifndef FE_RNT_OPT
-#define FE_RNT_OPT 128
-#endif
-constexpr int FE_RNT = FE_RNT_OPT;   // workgroup size of the reduction: 128 threads with eight records each (two waves per barrier; 256 threads: front end 1.154-1.161 against
-                                     // 1.106-1.110 ms on one box, tools/gpu_fe_ab2.sh; 512 threads were 13 % slower in round 4; 64 threads leave two waves per SIMD by LDS)
-#ifndef FE_WALK_OPT
-#define FE_WALK_OPT 4
-#endif
-constexpr int FE_WALK = FE_WALK_OPT; // members of a voxel whose gathers the ordered walk keeps in flight
-constexpr int FE_CAP = 1024;         // records of a bucket (or of a slice of it) the reduction holds in LDS
+constexpr int FE_RNT = 128;          // workgroup size of the reduction: 128 threads with eight records each (two waves per barrier; 256 threads: front end 1.154-1.161 against
+                                     // 1.106-1.110 ms on one box; 512 threads were 13 % slower in round 4; 64 threads leave two waves per SIMD by LDS)
+constexpr int FE_WAVES = 4;          // waves per SIMD asked of the reduction: what its registers give (5 / 6 spill 24 / 36 dwords: 0.45-0.51 against 0.45-0.46 ms)
+constexpr int FE_WALK = 4;           // members of a voxel whose gathers the ordered walk keeps in flight
+constexpr int FE_CAP = 1024;         // records of a bucket (or of a slice of it) the reduction orders in LDS at a time
 constexpr int FE_RPT = FE_CAP / FE_RNT;
 constexpr int FE_SLICES = 62;        // slices of a bucket with more than FE_CAP records
 constexpr int FE_ROWCAP = FE_LR * FE_NBMAX;      // padded rows (y, z) per cloud: at most 64 per bucket column
@@ -258,7 +251,6 @@ constexpr unsigned FE_NOSLOT = 0xffffffffu;      // no record for this point; as
 // one record to its slot
 __device__ __forceinline__ void fe_store_record(uint4* R, const FePoint& pt, int i, unsigned slot, int tid) {
     // (non-temporal stores here: 2.6x slower — the L2 merges the two halves of a record, and little else: a chunk adds ~4 records to a bucket)
-#if FE_PAIR_STORES
     // the two 16-byte halves of a record leave from ADJACENT lanes, so a store instruction carries 32 runs of 32 bytes instead of 64 of 16: lanes
     // 2j and 2j + 1 swap a half each (the even lane hands over its second half and takes the odd lane's first)
     const bool odd = tid & 1;
@@ -269,14 +261,8 @@ __device__ __forceinline__ void fe_store_record(uint4* R, const FePoint& pt, int
     const unsigned se = odd ? pslot : slot, so = odd ? slot : pslot;          // the even lane's record, the odd lane's record
     if (se != FE_NOSLOT) R[2 * (size_t)se + (odd ? 1 : 0)] = odd ? make_uint4(g0, g1, g2, g3) : make_uint4(a0, a1, a2, a3);
     if (so != FE_NOSLOT) R[2 * (size_t)so + (odd ? 1 : 0)] = odd ? make_uint4(b0, b1, b2, b3) : make_uint4(g0, g1, g2, g3);
-#else
-    if (slot != FE_NOSLOT) {
-        R[2 * (size_t)slot] = make_uint4(__float_as_uint(pt.x), __float_as_uint(pt.y), __float_as_uint(pt.z), (uint32_t)i);
-        R[2 * (size_t)slot + 1] = make_uint4(pt.w[0], pt.w[1], pt.w[2], pt.w[3]);
-    }
-#endif
 }
-// MODE 0: every bucket (ssdr_grid_subsample_batch_dev, and the staged reduction under SSDR_FE_SCATTER_PRUNE=0).  The staged reduction knows stage 1's buckets before
+// MODE 0: every bucket (ssdr_grid_subsample_batch_dev, and the records of a room plan).  The staged reduction knows stage 1's buckets before
 // a record is written (fe_tile_order runs first and leaves one flag per bucket), so MODE 1 writes the records of the flagged buckets only: the cursor of every
 // other bucket is FE_NOSLOT from the start, and a point that finds it gets no slot and no store (a lane pair with one such point stores one record's two halves).  The layout
 // (boff, cntm) is that of MODE 0: an unflagged bucket's range is simply not written, and nobody reads it — unless its room goes on to stage 2: MODE 2, launched behind
@@ -342,20 +328,17 @@ __global__ __launch_bounds__(FE_SNT) void fe_scatter(FeTab t, const float* __res
 // ---- reduction: one workgroup per bucket ------------------------------------------------------------------------------------
 struct FeRedArgs {
     FeTab t; const FeItem* items; GsParams* prm; int* counters; const float* rcp;
-    const uint4* rec; uint4* rows; uint4* wrec; unsigned* nocc; unsigned* trow; unsigned char* lrc; int fdim, ldim;
+    const uint4* rec; uint4* rows; unsigned* nocc; unsigned* trow; unsigned char* lrc; int fdim, ldim;
 };
 // rec: the records, read only — the call's own scatter left them in the per-stream buffer, or a room plan holds them (FePlan::rec).  rows: where the rows region
-// starts (ovf_cap rows): behind the n_total records of the per-stream buffer, or that whole buffer when the records are the plan's.  wrec: the per-stream record
-// buffer as the LDS-image variant writes it (a bucket's rows over its own records); never a plan's.
+// starts (ovf_cap = n_total rows: at most one per point): behind the n_total records of the per-stream buffer, or that whole buffer when the records are the plan's.
 
-// IMG: the bucket's (or slice's) records are also kept in LDS and the ordered walk reads them there — 51 KB per workgroup, three workgroups per CU.
-// !IMG: the walk reads the records where the scatter left them (the workgroup has just streamed them: L2) and the rows go to the overflow region —
-// 19 KB per workgroup, the occupancy is the registers'.
-template <bool IMG>
+// The ordered walk reads the records where the scatter left them (the workgroup has just streamed them: L2) and every bucket's rows go to the rows region: 19 KB of
+// LDS per workgroup, the occupancy is the registers'.  (A variant that also kept the bucket's records in LDS and wrote its rows over them — 51 KB per workgroup, three
+// workgroups per CU — measured on one box: fe_reduce 0.51-0.56 against 0.45-0.46 ms, front end 1.23-1.26 against 1.16-1.18 ms, 178.2-178.7 against 180.9-181.8 Mpoints/s.)
 struct FeRedLds {
-    uint4 rec[IMG ? FE_CAP * 2 : 1];       // IMG: the records of the bucket (or slice), in arrival order
     unsigned midx[FE_CAP];                 // per voxel segment: the members' indices, in arrival order
-    unsigned short perm[FE_CAP];           // per voxel segment: the members' positions in `rec` (IMG) / among the bucket's records (!IMG), by ascending index (input order)
+    unsigned short perm[FE_CAP];           // per voxel segment: the members' positions among the bucket's records, by ascending index (input order)
     unsigned cnt[FE_VMAX + 1];             // histogram, then start of every voxel's segment
     union {
         unsigned fill[FE_VMAX];            // slices: members of a voxel seen so far (while a slice's records arrive)
@@ -365,7 +348,7 @@ struct FeRedLds {
     unsigned short orank[FE_VMAX + 2];     // occupied voxels in front of a voxel
     unsigned short slice[FE_SLICES + 2];
     unsigned long long sw[FE_RNT / 64];
-    int nq, nslice, bad, nslow; unsigned ovf;
+    int nslice, bad, nslow; unsigned ovf;
 };
 
 // A label column's vote from the members themselves (labels outside [0,13), more than 255 members): rare, kept out of line so that its
@@ -384,8 +367,8 @@ __device__ __attribute__((noinline)) int fe_label_exact(const uint32_t* W, const
 // reference's vote takes the first maximum in the iteration order of its unordered_map<int,int>, which for labels in [0,13) is "first
 // seen last" (voxel_label.hpp).  Labels outside [0,13) or more than 255 members: noted in L.slow, settled by a second pass.
 // s0 = start of the slice's first segment.  FD / LD >= 0: row layout known at compile time.
-template <int FD, int LD, bool IMG>
-__device__ __forceinline__ void fe_reduce_voxels(FeRedLds<IMG>& L, const FeRedArgs& a, int* status, int o_begin, int o_end, unsigned s0, uint4* rows, const uint4* __restrict__ Rg) {
+template <int FD, int LD>
+__device__ __forceinline__ void fe_reduce_voxels(FeRedLds& L, const FeRedArgs& a, int* status, int o_begin, int o_end, unsigned s0, uint4* rows, const uint4* __restrict__ Rg) {
     const int fdim = FD >= 0 ? FD : a.fdim, ldim = LD >= 0 ? LD : a.ldim;
     const int half = (int)threadIdx.x & 1;
     for (int o = o_begin + ((int)threadIdx.x >> 1); o < o_end; o += FE_RNT / 2) {
@@ -400,7 +383,7 @@ __device__ __forceinline__ void fe_reduce_voxels(FeRedLds<IMG>& L, const FeRedAr
 #pragma unroll
             for (int h = 0; h < FE_WALK; ++h) p[h] = L.perm[min(j + h, e - 1)];
 #pragma unroll
-            for (int h = 0; h < FE_WALK; ++h) w[h] = IMG ? L.rec[2 * p[h] + half] : Rg[2 * (size_t)p[h] + half];
+            for (int h = 0; h < FE_WALK; ++h) w[h] = Rg[2 * (size_t)p[h] + half];
 #pragma unroll
             for (int h = 0; h < FE_WALK; ++h) {
                 if (j + h < e) {
@@ -447,7 +430,7 @@ __device__ __forceinline__ void fe_reduce_voxels(FeRedLds<IMG>& L, const FeRedAr
     }
     __syncthreads();
     if (L.nslow) {
-        const uint32_t* W = IMG ? reinterpret_cast<const uint32_t*>(L.rec) : reinterpret_cast<const uint32_t*>(Rg);
+        const uint32_t* W = reinterpret_cast<const uint32_t*>(Rg);
         for (int t = (int)threadIdx.x; t < L.nslow; t += FE_RNT) {
             const int o = o_begin + (L.slow[t] & 1023), hf = (L.slow[t] >> 10) & 1;
             const unsigned mask = L.slow[t] >> 11;
@@ -460,8 +443,7 @@ __device__ __forceinline__ void fe_reduce_voxels(FeRedLds<IMG>& L, const FeRedAr
 }
 
 // segment starts, the occupied voxels and their ranks from the histogram in L.cnt (V = 512 or 1024 voxels)
-template <bool IMG>
-__device__ __forceinline__ void fe_segments(FeRedLds<IMG>& L, int V) {
+__device__ __forceinline__ void fe_segments(FeRedLds& L, int V) {
     constexpr int EM = FE_VMAX / FE_RNT;
     const int tid = threadIdx.x, E = V / FE_RNT;           // 2 or 4 voxels per thread (256 threads)
     unsigned c4[EM]; unsigned tot = 0, occ = 0;
@@ -481,24 +463,14 @@ __device__ __forceinline__ void fe_segments(FeRedLds<IMG>& L, int V) {
     __syncthreads();
 }
 
-#ifdef SSDR_FE_STAMPS
-#define FE_STAMP(k) do { if (tid == 0) { const long long t_ = clock64(); t_acc[k] += (unsigned long long)(t_ - t_last); t_last = t_; } } while (0)
-#else
-#define FE_STAMP(k) do { } while (0)
-#endif
-// One workgroup per bucket (work items dealt round robin).  A bucket of at most FE_CAP records is read once: its records go to LDS as they
-// arrive, with the voxel histogram's returning atomics handing every record its arrival slot inside its voxel.  A larger bucket is cut into
-// slices of consecutive voxels (at most FE_CAP records each) after a histogram pass, and read again once per slice.
-#ifndef FE_RED_WAVES
-#define FE_RED_WAVES 4          // waves per SIMD asked of the no-image variant (A/B builds: -DFE_RED_WAVES=5 / 6 spill 24 / 36 dwords)
-#endif
-template <int FD, int LD, bool IMG>
-__global__ __launch_bounds__(FE_RNT) SSDR_WAVES_PER_EU(IMG ? 2 : FE_RED_WAVES) void fe_reduce(FeRedArgs a) {
-    __shared__ FeRedLds<IMG> L;
+// One workgroup per bucket (work items dealt round robin).  A bucket of at most FE_CAP records has the first halves of its records read once, the voxel
+// histogram's returning atomics handing every record its arrival slot inside its voxel.  A larger bucket is cut into slices of consecutive voxels (at most
+// FE_CAP records each) after a histogram pass, and its first halves are read again once per slice.  (Where the time goes, by clock stamps around the phases: load +
+// histogram 27 %, segments 6 %, rank 15 %, ordered walk 44 %, tail 7 %.)
+template <int FD, int LD>
+__global__ __launch_bounds__(FE_RNT) SSDR_WAVES_PER_EU(FE_WAVES) void fe_reduce(FeRedArgs a) {
+    __shared__ FeRedLds L;
     const int tid = threadIdx.x;
-#ifdef SSDR_FE_STAMPS
-    long long t_last = clock64(); unsigned long long t_acc[5] = {0, 0, 0, 0, 0};
-#endif
     const int nitems = a.counters[0];
     for (int i = blockIdx.x; i < nitems; i += (int)gridDim.x) {
         const FeItem it = a.items[i];
@@ -508,7 +480,7 @@ __global__ __launch_bounds__(FE_RNT) SSDR_WAVES_PER_EU(IMG ? 2 : FE_RED_WAVES) v
         const bool fast = n <= FE_CAP;
         const uint4* R = a.rec + 2 * (size_t)it.base;
         for (int v = tid; v <= V; v += FE_RNT) L.cnt[v] = 0;
-        if (tid == 0) { L.bad = 0; L.nq = 0; L.nslow = 0; }
+        if (tid == 0) { L.bad = 0; L.nslow = 0; }
         __syncthreads();
         // histogram over the bucket's voxels; FE_RPT records per thread, their loads issued together.  The fast path keeps every record's
         // voxel and arrival slot inside the voxel (what the returning atomic hands out) in registers until the segments are known
@@ -516,16 +488,15 @@ __global__ __launch_bounds__(FE_RNT) SSDR_WAVES_PER_EU(IMG ? 2 : FE_RED_WAVES) v
 #pragma unroll
         for (int k = 0; k < FE_RPT; ++k) { vv[k] = 0; uu[k] = 0u; ix[k] = 0u; }
         if (fast) {
-            // (x, y, z, index) is the FIRST half of a record: without the LDS image this pass reads 16 of its 32 bytes
-            uint4 r0[FE_RPT], r1[IMG ? FE_RPT : 1];
+            // (x, y, z, index) is the FIRST half of a record: this pass reads 16 of its 32 bytes
+            uint4 r0[FE_RPT];
 #pragma unroll
-            for (int k = 0; k < FE_RPT; ++k) { const size_t p = (size_t)min(tid + k * FE_RNT, n - 1); r0[k] = R[2 * p]; if (IMG) r1[k] = R[2 * p + 1]; }
+            for (int k = 0; k < FE_RPT; ++k) r0[k] = R[2 * (size_t)min(tid + k * FE_RNT, n - 1)];
 #pragma unroll
             for (int k = 0; k < FE_RPT; ++k) {
-                const int p = tid + k * FE_RNT;
                 vv[k] = fe_vid(it, __uint_as_float(r0[k].x), __uint_as_float(r0[k].y), __uint_as_float(r0[k].z));
                 ix[k] = r0[k].w;
-                if (p < n) { uu[k] = atomicAdd(&L.cnt[vv[k]], 1u); if (IMG) { L.rec[2 * p] = r0[k]; L.rec[2 * p + 1] = r1[IMG ? k : 0]; } }
+                if (tid + k * FE_RNT < n) uu[k] = atomicAdd(&L.cnt[vv[k]], 1u);
             }
         } else {
             for (int p0 = 0; p0 < n; p0 += FE_CAP) {
@@ -538,11 +509,8 @@ __global__ __launch_bounds__(FE_RNT) SSDR_WAVES_PER_EU(IMG ? 2 : FE_RED_WAVES) v
             }
         }
         __syncthreads();
-        FE_STAMP(0);
         fe_segments(L, V);
-        FE_STAMP(1);
         const int nocc = L.orank[V];
-        uint4* rows = IMG ? a.wrec + 2 * (size_t)it.base : nullptr;           // the bucket's rows go over its own records (all of them are in LDS by now) ...
         unsigned sg[FE_RPT], eg[FE_RPT];
 #pragma unroll
         for (int k = 0; k < FE_RPT; ++k) { sg[k] = 0u; eg[k] = 0u; }
@@ -555,13 +523,10 @@ __global__ __launch_bounds__(FE_RNT) SSDR_WAVES_PER_EU(IMG ? 2 : FE_RED_WAVES) v
         }
         if (tid == 0) {
             if (fast) { L.nslice = 1; L.slice[0] = 0; L.slice[1] = (unsigned short)V; }
-            if (!fast || !IMG) {
-                // ... unless the bucket is cut into slices that are read again (or the walk reads the records in place): its rows then go to the
-                // overflow region behind the records
-                const unsigned at = (unsigned)atomicAdd(&a.counters[3], nocc);
-                L.ovf = at + (unsigned)nocc <= (unsigned)a.t.ovf_cap ? at : 0xffffffffu;
-                if (L.ovf == 0xffffffffu) L.bad = 1;
-            }
+            // the bucket's place in the rows region
+            const unsigned at = (unsigned)atomicAdd(&a.counters[3], nocc);
+            L.ovf = at + (unsigned)nocc <= (unsigned)a.t.ovf_cap ? at : 0xffffffffu;
+            if (L.ovf == 0xffffffffu) L.bad = 1;
             if (!fast) {
                 int ns = 0, v = 0; L.slice[0] = 0;
                 while (v < V && ns < FE_SLICES) {
@@ -592,32 +557,29 @@ __global__ __launch_bounds__(FE_RNT) SSDR_WAVES_PER_EU(IMG ? 2 : FE_RED_WAVES) v
             }
             __syncthreads();
         }
-        if ((!fast || !IMG) && !L.bad) rows = a.rows + 2 * (size_t)L.ovf;
         const size_t tb = (size_t)r * FE_NBMAX + b;
         if (L.bad) {           // a voxel of more than FE_CAP points (or more slices / overflow rows than there is room for): not this entry point's case
-            if (tid == 0) { atomicOr(&prm->status, 4); a.nocc[tb] = 0u; a.trow[tb] = 0u; }
+            if (tid == 0) { atomicOr(&prm->status, 4); a.nocc[tb] = 0u; a.trow[tb] = 0u; }          // (no rows: what makes fe_move skip the bucket)
             for (int l = tid; l < FE_LR; l += FE_RNT) a.lrc[tb * FE_LR + l] = 0;
         } else {
+            uint4* rows = a.rows + 2 * (size_t)L.ovf;
             for (int si = 0; si < L.nslice; ++si) {
                 const int v0 = L.slice[si], v1 = L.slice[si + 1];
                 const unsigned s0 = L.cnt[v0];
                 const int ns = (int)(L.cnt[v1] - s0);
-                if (ns > 0 && !fast) {          // the slice's records, read again; then L.rec / L.perm as the fast path leaves them
+                if (ns > 0 && !fast) {          // the slice's records, read again; then L.midx / L.perm as the fast path leaves them
                     __syncthreads();
-                    if (tid == 0) L.nq = 0;
                     for (int v = v0 + tid; v < v1; v += FE_RNT) L.fill[v] = 0u;
                     __syncthreads();
                     for (int p0 = 0; p0 < n; p0 += FE_CAP) {
-                        uint4 q0[FE_RPT], q1[IMG ? FE_RPT : 1];
+                        uint4 q0[FE_RPT];
 #pragma unroll
-                        for (int k = 0; k < FE_RPT; ++k) { const size_t p = (size_t)min(p0 + tid + k * FE_RNT, n - 1); q0[k] = R[2 * p]; if (IMG) q1[k] = R[2 * p + 1]; }
+                        for (int k = 0; k < FE_RPT; ++k) q0[k] = R[2 * (size_t)min(p0 + tid + k * FE_RNT, n - 1)];
 #pragma unroll
                         for (int k = 0; k < FE_RPT; ++k) {
                             const int v = fe_vid(it, __uint_as_float(q0[k].x), __uint_as_float(q0[k].y), __uint_as_float(q0[k].z));
                             if (p0 + tid + k * FE_RNT < n && v >= v0 && v < v1) {
-                                int q;
-                                if (IMG) { q = atomicAdd(&L.nq, 1); L.rec[2 * q] = q0[k]; L.rec[2 * q + 1] = q1[IMG ? k : 0]; }
-                                else q = p0 + tid + k * FE_RNT;          // the record's place among the bucket's own (<= FE_SLICES * FE_CAP < 65536)
+                                const int q = p0 + tid + k * FE_RNT;          // the record's place among the bucket's own (<= FE_SLICES * FE_CAP < 65536)
                                 // (index, position) pairs of a voxel, in arrival order: midx holds the indices, perm the positions until the ranks are known
                                 const unsigned at = L.cnt[v] - s0 + atomicAdd(&L.fill[v], 1u);
                                 L.midx[at] = q0[k].w; L.perm[at] = (unsigned short)q;
@@ -639,20 +601,14 @@ __global__ __launch_bounds__(FE_RNT) SSDR_WAVES_PER_EU(IMG ? 2 : FE_RED_WAVES) v
                     if (tid == 0) L.nslow = 0;      // (L.slow shares its storage with L.fill)
                     __syncthreads();
                 }
-                FE_STAMP(2);
-                if (ns > 0) fe_reduce_voxels<FD, LD, IMG>(L, a, &prm->status, L.orank[v0], L.orank[v1], s0, rows, R);
-                FE_STAMP(3);
+                if (ns > 0) fe_reduce_voxels<FD, LD>(L, a, &prm->status, L.orank[v0], L.orank[v1], s0, rows, R);
             }
             // what the move needs: number of rows, where they are, occupied voxels per local row (y, z)
-            if (tid == 0) { a.nocc[tb] = (unsigned)nocc; a.trow[tb] = (fast && IMG) ? it.base : 0x80000000u | L.ovf; }
+            if (tid == 0) { a.nocc[tb] = (unsigned)nocc; a.trow[tb] = L.ovf; }
             for (int l = tid; l < FE_LR; l += FE_RNT) a.lrc[tb * FE_LR + l] = (unsigned char)(L.orank[(l + 1) << it.sx] - L.orank[l << it.sx]);
         }
         __syncthreads();
-        FE_STAMP(4);
     }
-#ifdef SSDR_FE_STAMPS
-    if (tid == 0) for (int k = 0; k < 5; ++k) atomicAdd(reinterpret_cast<unsigned long long*>(a.counters) + 8 + k, t_acc[k]);
-#endif
 }
 
 // occupied voxels of every padded row (iy, iz) of a cloud, and in front of every bucket inside its row (keys grow along x first)
@@ -702,7 +658,7 @@ __global__ __launch_bounds__(FE_NT) void fe_rowscan(const FeGeom* __restrict__ g
 
 // one wave per bucket: its rows to their final places
 struct FeMoveArgs {
-    FeTab t; const FeGeom* geom; const FeItem* items; const int* counters; const uint4* rec; const uint4* rows; const unsigned* nocc; const unsigned* trow;          // rec / rows: FeRedArgs' wrec / rows
+    FeTab t; const FeGeom* geom; const FeItem* items; const int* counters; const uint4* rows; const unsigned* nocc; const unsigned* trow;          // rows: FeRedArgs' rows; trow: a bucket's first row in it
     const unsigned char* lrc; const unsigned short* pre; const unsigned* rowbase; int fdim, ldim; float* out_p; float* out_f; int* out_c;
 };
 // FD / LD >= 0: row layout known at compile time (the hot path's 3 features + 1 label: one 12-byte store each for the position and the features instead of
@@ -718,8 +674,7 @@ __global__ __launch_bounds__(BS) void fe_move(FeMoveArgs a) {
         const FeGeom g = a.geom[r];
         const size_t tb = (size_t)r * FE_NBMAX + b;
         const int nocc = (int)a.nocc[tb];
-        const unsigned tr = a.trow[tb];
-        const uint4* rows = (tr & 0x80000000u) ? a.rows + 2 * (size_t)(tr & 0x7fffffffu) : a.rec + 2 * (size_t)tr;
+        const uint4* rows = a.rows + 2 * (size_t)a.trow[tb];
         const int by = (b / g.nbx) % g.nby, bz = b / (g.nbx * g.nby);
         // occupied voxels of the bucket in front of every local row
         const unsigned mine = a.lrc[tb * FE_LR + lane];
@@ -780,12 +735,15 @@ __global__ __launch_bounds__(BS) void fe_move(FeMoveArgs a) {
 // their count, every room's status and grid parameters — which is a function of the rooms' points and dl alone: a call with a plan reads those tables and
 // writes none of them; everything that depends on the centres (the order, the flags, the records, nocc / lrc / trow, the rows) stays per call.
 constexpr int FE_TO_NMAX = 8192;     // non-empty buckets of a room the order is sorted for (one LDS word each); a room with more is reduced whole
-constexpr int FE_TO_KBITS = 14;      // low bits of a sort word: the bucket (FE_NBMAX = 2^14); above them 18 bits of the least distance's pattern
+constexpr int FE_K1_MULT = 6;        // stage 1's size in tile sizes.  A stage costs the latency of a bucket's reduction (~100 us) however few buckets it holds, so the first stage should
+                                     // usually be the last; a smaller one saves scattered writes, and a miss costs a second read of the room.  One box, step of 16 rooms: 2, not widened
+                                     // (a probe for rho alone): 3.053-3.065 ms; 6: 2.962-2.971; 7 the same as 6; with the pruned scatter 4: 3.148-3.169
+constexpr int FE_TO_KBITS = 14;     // low bits of a sort word: the bucket (FE_NBMAX = 2^14); above them 18 bits of the least distance's pattern
 static_assert(FE_NBMAX == 1 << FE_TO_KBITS, "bucket bits of the order's sort words");
 struct FeCentres { float c[3 * RADIX_MAX_SEG]; };
 struct FeTileArgs {
     FeTab t; FeCentres cen; const FeGeom* geom; const unsigned* tot; const unsigned* boff; unsigned* nocc; unsigned char* lrc; unsigned char* flag;
-    unsigned* okey; float* odmax; unsigned* ocum; FeItem* work; int* counters; FeTileInfo* info; int num_points, k1_mult, k1_widen;
+    unsigned* okey; float* odmax; unsigned* ocum; FeItem* work; int* counters; FeTileInfo* info; int num_points;
     unsigned long long* given;          // fe_scatter_counters when the records are a room plan's and no scatter runs to count them (else NULL): per room, the records the stages were given
 };
 // per stage s = 1..3 a block of 8 counters behind the whole-room ones: [0] items of the stage's work list, [3] the overflow rows' cursor
@@ -886,7 +844,7 @@ __global__ __launch_bounds__(FE_NT) void fe_tile_order(FeTileArgs a) {
             __syncthreads();
         }
     }
-    const unsigned long long want = (unsigned long long)a.k1_mult * (unsigned long long)a.num_points;
+    const unsigned long long want = (unsigned long long)FE_K1_MULT * (unsigned long long)a.num_points;
     unsigned long long carry = 0;
     for (int i0 = 0; i0 < n; i0 += FE_NT) {
         const int i = i0 + tid;
@@ -904,7 +862,7 @@ __global__ __launch_bounds__(FE_NT) void fe_tile_order(FeTileArgs a) {
     }
     __syncthreads();
     int k1 = s_k1;
-    if (a.k1_widen && k1 < n) {          // every rank whose least distance does not exceed the greatest distance of a rank below k1: stage 1 can then pass the check itself
+    if (k1 < n) {         // every rank whose least distance does not exceed the greatest distance of a rank below k1: stage 1 can then pass the check itself
         if (tid == 0) s_m = 0u;
         __syncthreads();
         for (int i = tid; i < k1; i += FE_NT) {
@@ -993,10 +951,11 @@ __global__ __launch_bounds__(FE_NT) void fe_tile_plan(FeTileArgs a) {
     for (int i = lo + tid; i < hi; i += FE_NT) a.work[(size_t)s_base + (i - lo)] = fe_tile_item(a, g, r, (int)(key[i] & (FE_NBMAX - 1)));
 }
 
+// ---- the launcher: environment, plan, launch ------------------------------------------------------------------------------------------------------
 struct FeState {
     DevBuf partial, geom, cntm, tot, boff, items, counters, rec, nocc, trow, lrc, pre, rowcnt, rcp; bool rcp_ready = false;
     DevBuf okey, odmax, ocum, work, tinfo; int tile_clouds = 0;          // the staged reduction's tables; rooms of the last call if it was staged
-    DevBuf flag; bool pruned = false; std::vector<long long> room_n;      // [room][FE_NBMAX] bytes: stage 1 reduces this bucket; the last staged call: pruned scatter? its rooms' points
+    DevBuf flag; std::vector<long long> room_n;                          // [room][FE_NBMAX] bytes: stage 1 reduces this bucket; the last staged call's rooms' points
 };
 
 // the room table of a call, as every kernel takes it
@@ -1011,7 +970,7 @@ int fe_room_table(const int64_t* room_off, size_t nr, FeTab& t) {
     t.off[nr] = (int)room_off[nr];
     t.n_total = (int)room_off[nr];
     t.chunks_max = (maxn + FE_CH - 1) / FE_CH;
-    t.ovf_cap = 0;
+    t.ovf_cap = t.n_total;          // the rows region: every bucket's rows go there, at most one row per point
     return SSDR_OK;
 }
 
@@ -1027,6 +986,35 @@ void fe_launch_tables(const FeTab& t, const float* d_p, float dl, GsParams* prm,
     hipLaunchKernelGGL(fe_bscan, dim3(R), dim3(FE_NT), 0, s, t, T.geom, T.tot, T.boff, T.items, counters);
 }
 
+// The one scatter launcher: the input rows into `rec` by the tables' layout.  mode 0: every record (flag / info / nscat unused: NULL); 1: the records of the flagged
+// buckets; 2: those of the unflagged buckets of the rooms info sends on to stage 2; 1 and 2 count what they wrote per room into nscat.
+struct FeInputs { const float* p; const float* f; int fdim; const int* c; int ldim; };
+void fe_launch_scatter(int mode, const FeTab& t, const FeInputs& in, const FeTables& T, uint4* rec, const unsigned char* flag, const FeTileInfo* info, unsigned long long* nscat,
+                       hipStream_t s) {
+    using Kernel = decltype(&fe_scatter<3, 1, 0>);          // [the hot path's rows (3 features + 1 label) or any][mode]
+    static const Kernel kernel[2][3] = {{fe_scatter<-1, -1, 0>, fe_scatter<-1, -1, 1>, fe_scatter<-1, -1, 2>}, {fe_scatter<3, 1, 0>, fe_scatter<3, 1, 1>, fe_scatter<3, 1, 2>}};
+    hipLaunchKernelGGL(kernel[in.fdim == 3 && in.ldim == 1][mode], dim3(t.chunks_max, (unsigned)t.nr), dim3(FE_SNT), 0, s, t, in.p, in.f, in.fdim, in.c, in.ldim, T.geom, T.cntm,
+                       T.boff, rec, flag, info, nscat);
+}
+void fe_launch_reduce(int grid, const FeRedArgs& ra, hipStream_t s) {
+    hipLaunchKernelGGL((ra.fdim == 3 && ra.ldim == 1 ? fe_reduce<3, 1> : fe_reduce<-1, -1>), dim3(grid), dim3(FE_RNT), 0, s, ra);
+}
+
+// The process-wide switches, read once (tests/test_subsample_paths.py gives a setting a child process of its own).  The two switches of a plan's creation,
+// SSDR_FE_PLAN_RECORDS and SSDR_FE_PLAN_RECORDS_MAX_MB, are read at every frontend_plan_build instead: the tests set them in-process.
+struct FeEnv {
+    int wgs;             // SSDR_FE_WGS: workgroups per CU of the unstaged reduction, not capped by the points (unset: 0 = the default below)
+    int move_wgs;        // SSDR_FE_MOVE_WGS: workgroups per CU of fe_move (unset: 32)
+};
+const FeEnv& fe_env() {
+    static const FeEnv env = [] {
+        auto num = [](const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; };
+        return FeEnv{num("SSDR_FE_WGS", 0), num("SSDR_FE_MOVE_WGS", 32)};
+    }();
+    return env;
+}
+long fe_env_long(const char* name, long dflt) { const char* e = getenv(name); return e && e[0] ? atol(e) : dflt; }
+
 }  // namespace
 
 // A room plan: the tables of fe_launch_tables in buffers of its own (not the per-stream scratch: calls on any stream read them, a call without a plan on the same
@@ -1035,8 +1023,7 @@ void fe_launch_tables(const FeTab& t, const float* d_p, float dl, GsParams* prm,
 // every-bucket scatter (MODE 0) runs once, at build, and a call with such a plan launches no scatter and reads none of points / features / labels: fe_reduce reads
 // the plan's records in place (it never writes them: its rows go to the per-stream rows region).  The plan holds the inputs rearranged and counts of them, never a
 // sum or a vote.  Switches, read when a plan is created: SSDR_FE_PLAN_RECORDS=0 builds a plan without records (calls scatter per step as without them: A/B runs);
-// SSDR_FE_PLAN_RECORDS_MAX_MB (default 4096): a plan whose records would be larger is built without them.  Under SSDR_FE_IMAGE=1 (the LDS-image reduction writes a
-// bucket's rows over its records) a call keeps scattering into the per-stream buffer and leaves the plan's records alone.
+// SSDR_FE_PLAN_RECORDS_MAX_MB (default 4096): a plan whose records would be larger is built without them.
 struct FePlan {
     DevBuf partial, geom, cntm, tot, boff, items, counters, prm;
     DevBuf rec; size_t record_bytes = 0;          // the rooms' records, every bucket's where (boff, cntm) put them: 32 B x n_total, or none (record_bytes 0: calls scatter per step)
@@ -1049,10 +1036,52 @@ struct FePlan {
     ~FePlan() { if (built) (void)hipEventDestroy(built); }
 };
 
-bool frontend_fits(size_t fdim, size_t ldim) { return 3 + fdim + ldim <= 7; }
+namespace {
 
-// (environment switches of a plan are read at every creation, not once per process: a test sets them in-process)
-static long fe_env_long(const char* name, long dflt) { const char* e = getenv(name); return e && e[0] ? atol(e) : dflt; }
+// What one call enqueues.  Four kinds:
+//
+//   call                                              tables                         order                                scatter                              reduction
+//   unstaged (no centres; a plan never arrives here)  own five launches              none                                 MODE 0                               one launch over all items
+//   staged, no plan                                   own five launches              fe_tile_order before the scatter     MODE 1, then MODE 2 before stage 2   three stage launches
+//   staged, plan without records                      plan's tables + fe_plan_begin  the same                             the same                             the same
+//   staged, plan with records                         plan's tables + fe_plan_begin  the same, and it counts `given`      none                                 three stages reading plan->rec
+//
+// The order counts `given` (per room, the records the stages were given: FeTileArgs::given) exactly when no scatter runs to count them.
+enum FeKind { FE_UNSTAGED, FE_STAGED, FE_STAGED_PLAN, FE_STAGED_PLAN_REC };
+struct FeCall {
+    FeKind kind = FE_UNSTAGED;
+    bool staged() const { return kind != FE_UNSTAGED; }
+    bool planned() const { return kind == FE_STAGED_PLAN || kind == FE_STAGED_PLAN_REC; }
+    bool scatters() const { return kind != FE_STAGED_PLAN_REC; }
+    const uint4* rec = nullptr;          // the records where a plan holds them; NULL: the call's scatter leaves them at the start of the per-stream buffer
+    size_t rows_at = 0;                  // first row of the rows region (t.ovf_cap rows) in the per-stream buffer: behind the call's own records, or 0
+    size_t buf_bytes = 0;                // that buffer
+    int g_whole = 0, g_stage = 0, g_last = 0, g_move = 0;          // grids: the unstaged reduction; stages 1 and 2, stage 3; fe_move
+};
+
+// Launches nothing and reserves nothing.
+FeCall fe_call_plan(const FeTab& t, bool centres, const FePlan* plan, int num_cu, const FeEnv& env) {
+    FeCall c;
+    c.kind = !centres ? FE_UNSTAGED : !plan ? FE_STAGED : !plan->record_bytes ? FE_STAGED_PLAN : FE_STAGED_PLAN_REC;
+    if (!c.scatters()) c.rec = plan->rec.as<uint4>();
+    c.rows_at = c.scatters() ? (size_t)t.n_total : 0;
+    c.buf_bytes = 32 * (c.rows_at + (size_t)t.ovf_cap) + 64;
+    // The items (buckets) differ in size and are dealt to the workgroups round robin: with twice the resident workgroups (16 per CU: rounds 4-5) the
+    // kernel ended with its unluckiest workgroup; with ~ one workgroup per item the hardware's dispatcher does the balancing.  Same box, workgroups
+    // per CU (SSDR_FE_WGS): 16: 0.43 ms, 32: 0.39, 64: 0.35, **128: 0.338**, 256: 0.337, 512: 0.343, 4096: slower than 16 (front end 1.08 -> 1.00 ms,
+    // 198 -> 201 Mpoints/s).  Capped by the points (a bucket holds ~10^3 of them; workgroups beyond the item count exit at once).
+    const long cap = std::max<long>((long)num_cu * 16, (long)t.n_total / 64);
+    c.g_stage = (int)std::min<long>((long)num_cu * 128, cap);
+    c.g_whole = env.wgs > 0 ? (int)std::min<long>((long)num_cu * env.wgs, 1L << 30) : c.g_stage;
+    c.g_last = std::max(1, c.g_stage / 8);          // stage 3 is the exception: its workgroups take several items each
+    // a wave per item, round robin: 8 workgroups per CU give every wave two items of different sizes, 32 one (0.100 -> 0.094 ms; SSDR_FE_MOVE_WGS)
+    c.g_move = num_cu * env.move_wgs;
+    return c;
+}
+
+}  // namespace
+
+bool frontend_fits(size_t fdim, size_t ldim) { return 3 + fdim + ldim <= 7; }
 
 // the five launches of fe_launch_tables into a new plan's buffers, on `s`, and the every-bucket scatter into its records; the event lets a call on another stream wait for them
 int frontend_plan_build(const float* d_p, const float* d_f, size_t fdim, const int32_t* d_c, size_t ldim, const int64_t* room_off, size_t nr, float dl, hipStream_t s,
@@ -1072,13 +1101,7 @@ int frontend_plan_build(const float* d_p, const float* d_f, size_t fdim, const i
     fe_launch_tables(t, d_p, dl, P->prm.as<GsParams>(), P->tables(), P->counters.as<int>(), s);
     if (records) {
         // every record of every room with a grid (a room without one writes nothing), behind fe_bscan: the layout a call's own scatter would give
-        const FeTables T = P->tables();
-        if (fdim == 3 && ldim == 1)
-            hipLaunchKernelGGL((fe_scatter<3, 1, 0>), dim3(t.chunks_max, (unsigned)nr), dim3(FE_SNT), 0, s, t, d_p, d_f, (int)fdim, (const int*)d_c, (int)ldim, (const FeGeom*)T.geom,
-                               (const unsigned*)T.cntm, (const unsigned*)T.boff, P->rec.as<uint4>(), (const unsigned char*)nullptr, (const FeTileInfo*)nullptr, (unsigned long long*)nullptr);
-        else
-            hipLaunchKernelGGL((fe_scatter<-1, -1, 0>), dim3(t.chunks_max, (unsigned)nr), dim3(FE_SNT), 0, s, t, d_p, d_f, (int)fdim, (const int*)d_c, (int)ldim, (const FeGeom*)T.geom,
-                               (const unsigned*)T.cntm, (const unsigned*)T.boff, P->rec.as<uint4>(), (const unsigned char*)nullptr, (const FeTileInfo*)nullptr, (unsigned long long*)nullptr);
+        fe_launch_scatter(0, t, FeInputs{d_p, d_f, (int)fdim, (const int*)d_c, (int)ldim}, P->tables(), P->rec.as<uint4>(), nullptr, nullptr, nullptr, s);
         P->record_bytes = rec_bytes;
     }
     SSDR_HIP(hipGetLastError());
@@ -1121,19 +1144,15 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
                           float* d_op, float* d_of, int32_t* d_oc, int64_t* d_om, GsParams* prm, hipStream_t s, const float* centres, size_t num_points, const FePlan* plan) {
     FeState& S = per_stream<FeState>(s);
     S.tile_clouds = 0;
+    // 1. the room table
     FeTab t;
     SSDR_TRY(fe_room_table(room_off, nr, t));
-    // The reduction reads a bucket's records in place (no LDS image: 19 KB instead of 51 KB per workgroup, four workgroups per CU by registers) and every
-    // bucket's rows go to the overflow region, which then holds up to one row per point.  Measured on one box (tools/gpu_fe_ab.sh, round 5): fe_reduce 0.51-0.56
-    // -> 0.45-0.46 ms, front end 1.23-1.26 -> 1.16-1.18 ms, headline 178.2-178.7 -> 180.9-181.8 Mpoints/s; 5 / 6 waves per SIMD (spilling 24 / 36 dwords)
-    // 0.45-0.51 ms.  SSDR_FE_IMAGE=1 keeps the LDS-image kernel (A/B runs).
-    static const bool fe_image = [] { const char* e = getenv("SSDR_FE_IMAGE"); return e && e[0] == '1'; }();
-    static const int fe_wgs = [] { const char* e = getenv("SSDR_FE_WGS"); return e ? atoi(e) : 0; }();
-    static const int fe_pad = [] { const char* e = getenv("SSDR_FE_PADLDS"); return e ? atoi(e) : 0; }();      // (development: unused dynamic LDS caps the workgroups per CU)
-    t.ovf_cap = fe_image ? std::max(65536, t.n_total / 8) : t.n_total;
-    const unsigned R = (unsigned)nr;
-    SSDR_TRY(S.counters.reserve(256 + 8 * RADIX_MAX_SEG));
-    if (!plan) {
+    // 2. what this call enqueues
+    if (plan && !centres) { set_error("grid_subsample_batch: a room plan goes with centres"); return SSDR_ERR_INTERNAL; }
+    const FeCall call = fe_call_plan(t, centres != nullptr, plan, ctx().num_cu, fe_env());
+    // 3. the per-stream scratch
+    SSDR_TRY(S.counters.reserve(256 + 8 * RADIX_MAX_SEG)); SSDR_TRY(S.rcp.reserve(4 * (FE_CAP + 1)));
+    if (!call.planned()) {
         SSDR_TRY(S.partial.reserve(24 * (size_t)PB * nr)); SSDR_TRY(S.geom.reserve(sizeof(FeGeom) * nr));
         SSDR_TRY(S.cntm.reserve(4 * (size_t)FE_NBMAX * t.chunks_max * nr)); SSDR_TRY(S.tot.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.boff.reserve(4 * (size_t)(FE_NBMAX + 1) * nr));
         SSDR_TRY(S.items.reserve(sizeof(FeItem) * (size_t)FE_NBMAX * nr));
@@ -1141,54 +1160,44 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
     SSDR_TRY(S.nocc.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.trow.reserve(4 * (size_t)FE_NBMAX * nr));
     SSDR_TRY(S.lrc.reserve((size_t)FE_NBMAX * FE_LR * nr)); SSDR_TRY(S.pre.reserve(2 * (size_t)FE_NBMAX * FE_LR * nr));
     SSDR_TRY(S.rowcnt.reserve(4 * (size_t)FE_ROWCAP * nr));
-    // the records are the plan's: no scatter in this call, and the per-stream buffer holds the rows region alone (the LDS-image variant writes rows over records:
-    // it keeps its own scatter into the per-stream buffer)
-    const bool plan_rec = plan && plan->record_bytes && !fe_image;
-    SSDR_TRY(S.rec.reserve(32 * ((plan_rec ? 0 : (size_t)t.n_total) + t.ovf_cap) + 64));
-    if (!S.rcp_ready) {
-        SSDR_TRY(S.rcp.reserve(4 * (FE_CAP + 1)));
-        hipLaunchKernelGGL(fe_rcp_init, dim3((FE_CAP + 256) / 256), dim3(256), 0, s, S.rcp.as<float>());
-        S.rcp_ready = true;
-    }
-    // the centre-independent tables: this call's own (the per-stream scratch), or the plan's (read-only here; the only list the stages write is S.work)
-    FeTables own; own.partial = S.partial.as<float>(); own.geom = S.geom.as<FeGeom>(); own.cntm = S.cntm.as<unsigned>(); own.tot = S.tot.as<unsigned>();
-    own.boff = S.boff.as<unsigned>(); own.items = S.items.as<FeItem>();
-    const FeTables T = plan ? plan->tables() : own;
-    const FeGeom* geom = T.geom; int* counters = S.counters.as<int>(); const FeItem* items = T.items;
-    const unsigned* cntm = T.cntm; const unsigned* tot = T.tot; const unsigned* boff = T.boff;
-    FeRedArgs ra; ra.t = t; ra.items = items; ra.prm = prm; ra.counters = counters; ra.rcp = S.rcp.as<float>();
-    ra.rec = plan_rec ? plan->rec.as<uint4>() : S.rec.as<uint4>(); ra.rows = S.rec.as<uint4>() + (plan_rec ? 0 : 2 * (size_t)t.n_total); ra.wrec = S.rec.as<uint4>();
-    ra.nocc = S.nocc.as<unsigned>(); ra.trow = S.trow.as<unsigned>(); ra.lrc = S.lrc.as<unsigned char>(); ra.fdim = (int)fdim; ra.ldim = (int)ldim;
-    // the staged reduction (centres given).  Stage 1's buckets follow from the buckets' point counts, their boxes and the centres: all there after fe_bscan, so the
-    // order comes first and the scatter writes the records of those buckets only.  SSDR_FE_SCATTER_PRUNE=0 (development: A/B runs in one build) keeps the one
-    // scatter of every record, with the order behind it.
-    const bool staged = centres && !fe_image;
-    static const bool fe_scatter_prune = [] { const char* e = getenv("SSDR_FE_SCATTER_PRUNE"); return !(e && e[0] == '0'); }();
-    const bool prune = staged && fe_scatter_prune;
-    FeTileArgs ta;
-    if (staged) {
+    SSDR_TRY(S.rec.reserve(call.buf_bytes));
+    if (call.staged()) {
         SSDR_TRY(S.okey.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.odmax.reserve(4 * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.ocum.reserve(4 * (size_t)FE_NBMAX * nr));
         SSDR_TRY(S.work.reserve(sizeof(FeItem) * (size_t)FE_NBMAX * nr)); SSDR_TRY(S.tinfo.reserve(sizeof(FeTileInfo) * RADIX_MAX_SEG));
-        if (prune) SSDR_TRY(S.flag.reserve((size_t)FE_NBMAX * nr));
-        ta.t = t; ta.geom = geom; ta.tot = tot; ta.boff = boff; ta.nocc = ra.nocc; ta.lrc = ra.lrc;
-        ta.flag = prune ? S.flag.as<unsigned char>() : nullptr;
+        SSDR_TRY(S.flag.reserve((size_t)FE_NBMAX * nr));
+    }
+    // 4. the launches, in stream order.  The centre-independent tables are this call's own (the per-stream scratch) or the plan's (read-only here; the only list the
+    // stages write is S.work)
+    const unsigned R = (unsigned)nr;
+    FeTables own; own.partial = S.partial.as<float>(); own.geom = S.geom.as<FeGeom>(); own.cntm = S.cntm.as<unsigned>(); own.tot = S.tot.as<unsigned>();
+    own.boff = S.boff.as<unsigned>(); own.items = S.items.as<FeItem>();
+    const FeTables T = call.planned() ? plan->tables() : own;
+    int* counters = S.counters.as<int>();
+    const FeInputs in{d_p, d_f, (int)fdim, (const int*)d_c, (int)ldim};
+    FeRedArgs ra; ra.t = t; ra.items = T.items; ra.prm = prm; ra.counters = counters; ra.rcp = S.rcp.as<float>();
+    ra.rec = call.rec ? call.rec : S.rec.as<uint4>(); ra.rows = S.rec.as<uint4>() + 2 * call.rows_at;
+    ra.nocc = S.nocc.as<unsigned>(); ra.trow = S.trow.as<unsigned>(); ra.lrc = S.lrc.as<unsigned char>(); ra.fdim = (int)fdim; ra.ldim = (int)ldim;
+    // the staged reduction (centres given).  Stage 1's buckets follow from the buckets' point counts, their boxes and the centres: all there after fe_bscan, so the
+    // order comes first and the scatter writes the records of those buckets only
+    FeTileArgs ta;
+    if (call.staged()) {
+        ta.t = t; ta.geom = T.geom; ta.tot = T.tot; ta.boff = T.boff; ta.nocc = ra.nocc; ta.lrc = ra.lrc; ta.flag = S.flag.as<unsigned char>();
         for (size_t i = 0; i < 3 * nr; ++i) ta.cen.c[i] = centres[i];
         ta.okey = S.okey.as<unsigned>(); ta.odmax = S.odmax.as<float>(); ta.ocum = S.ocum.as<unsigned>(); ta.work = S.work.as<FeItem>(); ta.counters = counters;
         ta.info = S.tinfo.as<FeTileInfo>(); ta.num_points = (int)std::min<size_t>(num_points, 0x3fffffff);
-        static const int k1_mult = [] { const char* e = getenv("SSDR_FE_TILE_K1"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 64 ? v : 6; }();
-        // stage 1's size in tile sizes (development; measured on one box, step of 16 rooms: 2, not widened, i.e. a probe for rho alone: 3.053-3.065 ms; 6: 2.962-2.971;
-        // 7 the same as 6; two calls 3.149-3.176): a stage costs the latency of a bucket's reduction (~100 us) however few buckets it holds, so the
-        // first stage should usually be the last.  With the pruned scatter a smaller stage 1 also saves scattered writes, and a miss costs a second read of the room.
-        ta.k1_mult = k1_mult; ta.k1_widen = k1_mult != 2;
         // no scatter counts its records when they are the plan's: the order and the stage plan count what the stages are given, into the same words
-        ta.given = prune && plan_rec ? fe_scatter_counters(counters) : nullptr;
+        ta.given = call.scatters() ? nullptr : fe_scatter_counters(counters);
     }
     const unsigned char* flag = S.flag.as<unsigned char>(); const FeTileInfo* tinfo = S.tinfo.as<FeTileInfo>(); unsigned long long* nscat = fe_scatter_counters(counters);
+    if (!S.rcp_ready) {
+        hipLaunchKernelGGL(fe_rcp_init, dim3((FE_CAP + 256) / 256), dim3(256), 0, s, S.rcp.as<float>());
+        S.rcp_ready = true;
+    }
     // profiler sites (ssdr_prof_enable; bench.py's roofline leg): `work` = the algorithmic bytes a site is charged with — the one read of the inputs
     // (28 B per point) goes to the scatter, the one write of the rows (28 B per voxel: the count is the device's, bench.py adds it) to the reduction
     {
     ProfScope prof("fe_bbox_count_scan", s, 0.0);
-    if (plan) {
+    if (call.planned()) {
         // the plan's launches ran on its own stream: the first call on every other stream is ordered behind them
         if (s != plan->stream) {
             std::lock_guard<std::mutex> lk(plan->mu);
@@ -1196,79 +1205,39 @@ int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const
         }
         hipLaunchKernelGGL(fe_plan_begin, dim3(R), dim3(64), 0, s, plan->prm.as<GsParams>(), plan->counters.as<int>(), prm, counters);
     } else fe_launch_tables(t, d_p, dl, prm, own, counters, s);
-    if (prune) hipLaunchKernelGGL(fe_tile_order, dim3(R), dim3(FE_NT), 0, s, ta);
+    if (call.staged()) hipLaunchKernelGGL(fe_tile_order, dim3(R), dim3(FE_NT), 0, s, ta);
     }
-#define FE_LAUNCH_SCATTER(MODE)                                                                                                                                              \
-    do {                                                                                                                                                                     \
-        if (fdim == 3 && ldim == 1)                                                                                                                                          \
-            hipLaunchKernelGGL((fe_scatter<3, 1, MODE>), dim3(t.chunks_max, R), dim3(FE_SNT), 0, s, t, d_p, d_f, (int)fdim, (const int*)d_c, (int)ldim, geom, cntm, \
-                               boff, S.rec.as<uint4>(), flag, tinfo, nscat);                                                                                \
-        else                                                                                                                                                                 \
-            hipLaunchKernelGGL((fe_scatter<-1, -1, MODE>), dim3(t.chunks_max, R), dim3(FE_SNT), 0, s, t, d_p, d_f, (int)fdim, (const int*)d_c, (int)ldim, geom, cntm, \
-                               boff, S.rec.as<uint4>(), flag, tinfo, nscat);                                                                                \
-    } while (0)
-    if (!plan_rec) {
+    if (call.scatters()) {
     ProfScope prof("fe_scatter", s, (double)(12 + 4 * (fdim + ldim)) * (double)t.n_total);
-    if (prune) FE_LAUNCH_SCATTER(1);
-    else FE_LAUNCH_SCATTER(0);
+    fe_launch_scatter(call.staged() ? 1 : 0, t, in, T, S.rec.as<uint4>(), flag, tinfo, nscat, s);
     }
     {
     ProfScope prof("fe_reduce", s, 0.0);
-    if (staged) {
+    if (call.staged()) {
         // the same kernel per stage, over the stage's work list; the lists' lengths are the device's (workgroups beyond them exit at once)
-        const long cap = std::max<long>((long)ctx().num_cu * 16, (long)t.n_total / 64);
-        const int g = (int)std::min<long>((long)ctx().num_cu * 128, cap);
         ra.items = S.work.as<FeItem>();
         for (int stage = 1; stage <= 3; ++stage) {
-            if (stage == 1) { if (!prune) hipLaunchKernelGGL(fe_tile_order, dim3(R), dim3(FE_NT), 0, s, ta); }
-            else if (stage == 2) {
+            if (stage == 2) {
                 hipLaunchKernelGGL((fe_tile_plan<2>), dim3(R), dim3(FE_NT), 0, s, ta);
                 // the records stage 1 did not need, for the rooms that go on (a second read of their points); every other room's workgroups leave at once
-                if (prune && !plan_rec) FE_LAUNCH_SCATTER(2);
-            }
-            else hipLaunchKernelGGL((fe_tile_plan<3>), dim3(R), dim3(FE_NT), 0, s, ta);
+                if (call.scatters()) fe_launch_scatter(2, t, in, T, S.rec.as<uint4>(), flag, tinfo, nscat, s);
+            } else if (stage == 3) hipLaunchKernelGGL((fe_tile_plan<3>), dim3(R), dim3(FE_NT), 0, s, ta);
             ra.counters = fe_stage_counters(counters, stage);
-            const int gs = stage < 3 ? g : std::max(1, g / 8);          // stage 3 is the exception: its workgroups take several items each
-            if (fdim == 3 && ldim == 1) hipLaunchKernelGGL((fe_reduce<3, 1, false>), dim3(gs), dim3(FE_RNT), (size_t)fe_pad, s, ra);
-            else hipLaunchKernelGGL((fe_reduce<-1, -1, false>), dim3(gs), dim3(FE_RNT), (size_t)fe_pad, s, ra);
+            fe_launch_reduce(stage < 3 ? call.g_stage : call.g_last, ra, s);
         }
-        S.tile_clouds = (int)nr; S.pruned = prune;
+        S.tile_clouds = (int)nr;
         S.room_n.assign(nr, 0);
         for (size_t r = 0; r < nr; ++r) S.room_n[r] = (long long)(room_off[r + 1] - room_off[r]);
-    } else if (!fe_image) {
-        // The items (buckets) differ in size and are dealt to the workgroups round robin: with twice the resident workgroups (16 per CU: rounds 4-5) the
-        // kernel ended with its unluckiest workgroup; with ~ one workgroup per item the hardware's dispatcher does the balancing.  Same box, workgroups
-        // per CU (SSDR_FE_WGS): 16: 0.43 ms, 32: 0.39, 64: 0.35, **128: 0.338**, 256: 0.337, 512: 0.343, 4096: slower than 16 (front end 1.08 -> 1.00 ms,
-        // 198 -> 201 Mpoints/s).  Capped by the points (a bucket holds ~10^3 of them; workgroups beyond the item count exit at once).
-        const long cap = std::max<long>((long)ctx().num_cu * 16, (long)t.n_total / 64);
-        const int g = (int)std::min<long>((long)ctx().num_cu * (fe_wgs > 0 ? fe_wgs : 128), fe_wgs > 0 ? (1L << 30) : cap);
-        if (fdim == 3 && ldim == 1) hipLaunchKernelGGL((fe_reduce<3, 1, false>), dim3(g), dim3(FE_RNT), (size_t)fe_pad, s, ra);
-        else hipLaunchKernelGGL((fe_reduce<-1, -1, false>), dim3(g), dim3(FE_RNT), (size_t)fe_pad, s, ra);
-    } else if (fdim == 3 && ldim == 1) hipLaunchKernelGGL((fe_reduce<3, 1, true>), dim3(ctx().num_cu * (fe_wgs > 0 ? fe_wgs : 3)), dim3(FE_RNT), 0, s, ra);        // the hot path's rows
-    else hipLaunchKernelGGL((fe_reduce<-1, -1, true>), dim3(ctx().num_cu * (fe_wgs > 0 ? fe_wgs : 3)), dim3(FE_RNT), 0, s, ra);
+    } else fe_launch_reduce(call.g_whole, ra, s);
     }
     ProfScope prof_move("fe_rows_move", s, 0.0);
-    hipLaunchKernelGGL(fe_rowpre, dim3(256, R), dim3(BS), 0, s, geom, boff, S.lrc.as<unsigned char>(), S.pre.as<unsigned short>(), S.rowcnt.as<unsigned>());
-    hipLaunchKernelGGL(fe_rowscan, dim3(R), dim3(FE_NT), 0, s, geom, S.rowcnt.as<unsigned>(), prm, (long long*)d_om);
-    FeMoveArgs ma; ma.t = t; ma.geom = geom; ma.items = items; ma.counters = counters; ma.rec = ra.wrec; ma.rows = ra.rows; ma.nocc = S.nocc.as<unsigned>();
+    hipLaunchKernelGGL(fe_rowpre, dim3(256, R), dim3(BS), 0, s, T.geom, T.boff, S.lrc.as<unsigned char>(), S.pre.as<unsigned short>(), S.rowcnt.as<unsigned>());
+    hipLaunchKernelGGL(fe_rowscan, dim3(R), dim3(FE_NT), 0, s, T.geom, S.rowcnt.as<unsigned>(), prm, (long long*)d_om);
+    FeMoveArgs ma; ma.t = t; ma.geom = T.geom; ma.items = T.items; ma.counters = counters; ma.rows = ra.rows; ma.nocc = S.nocc.as<unsigned>();
     ma.trow = S.trow.as<unsigned>(); ma.lrc = S.lrc.as<unsigned char>(); ma.pre = S.pre.as<unsigned short>(); ma.rowbase = S.rowcnt.as<unsigned>(); ma.fdim = (int)fdim; ma.ldim = (int)ldim;
     ma.out_p = d_op; ma.out_f = d_of; ma.out_c = d_oc;
-    // a wave per item, round robin: 8 workgroups per CU give every wave two items of different sizes, 32 one (0.100 -> 0.094 ms; SSDR_FE_MOVE_WGS)
-    static const int mv_wgs = [] { const char* e = getenv("SSDR_FE_MOVE_WGS"); return e ? atoi(e) : 32; }();
-    if (fdim == 3 && ldim == 1) hipLaunchKernelGGL((fe_move<3, 1>), dim3(ctx().num_cu * mv_wgs), dim3(BS), 0, s, ma);
-    else hipLaunchKernelGGL((fe_move<-1, -1>), dim3(ctx().num_cu * mv_wgs), dim3(BS), 0, s, ma);
+    hipLaunchKernelGGL((fdim == 3 && ldim == 1 ? fe_move<3, 1> : fe_move<-1, -1>), dim3(call.g_move), dim3(BS), 0, s, ma);
     SSDR_HIP(hipGetLastError());
-#ifdef SSDR_FE_STAMPS
-    {
-        SSDR_HIP(hipStreamSynchronize(s));
-        unsigned long long h[8]; int hc[8];
-        SSDR_HIP(hipMemcpy(hc, counters, sizeof(hc), hipMemcpyDeviceToHost));
-        SSDR_HIP(hipMemcpy(h, reinterpret_cast<unsigned long long*>(counters) + 8, sizeof(h), hipMemcpyDeviceToHost));
-        fprintf(stderr, "fe_reduce: %d items, %d overflow rows; clock ticks per phase (sum over workgroups): load+hist %llu, segments %llu, rank %llu, voxels %llu, tail %llu\n",
-                hc[0], hc[3], h[0], h[1], h[2], h[3], h[4]);
-        SSDR_HIP(hipMemset(reinterpret_cast<unsigned long long*>(counters) + 8, 0, sizeof(h)));
-    }
-#endif
     return SSDR_OK;
 }
 
@@ -1290,16 +1259,16 @@ int frontend_tile_stats(hipStream_t s, int32_t* stage, int32_t* reduced, int32_t
     return SSDR_OK;
 }
 
-// what the scatter of the last staged call on `s` wrote, per room (waits for the stream): the records written (stage 1's pass plus the second pass of a room that went
-// on; -1 under SSDR_FE_SCATTER_PRUNE=0, where the one scatter of every record does not count) and the room's points; -1 / -1 when the call was not staged
+// what the stages of the last staged call on `s` were given, per room (waits for the stream): the records the scatter wrote (stage 1's pass plus the second pass of a
+// room that went on) — or, when a plan holds the records, the records of the same buckets, counted by the order — and the room's points; -1 / -1 when the call was not staged
 int frontend_scatter_stats(hipStream_t s, int64_t* scattered, int64_t* points, size_t nr) {
     FeState& S = per_stream<FeState>(s);
     SSDR_HIP(hipStreamSynchronize(s));
     std::vector<unsigned long long> h(nr);
     const bool staged = S.tile_clouds > 0 && (size_t)S.tile_clouds == nr;
-    if (staged && S.pruned) SSDR_HIP(hipMemcpy(h.data(), fe_scatter_counters(S.counters.as<int>()), sizeof(unsigned long long) * nr, hipMemcpyDeviceToHost));
+    if (staged) SSDR_HIP(hipMemcpy(h.data(), fe_scatter_counters(S.counters.as<int>()), sizeof(unsigned long long) * nr, hipMemcpyDeviceToHost));
     for (size_t r = 0; r < nr; ++r) {
-        if (scattered) scattered[r] = staged && S.pruned ? (int64_t)h[r] : -1;
+        if (scattered) scattered[r] = staged ? (int64_t)h[r] : -1;
         if (points) points[r] = staged ? (int64_t)S.room_n[r] : -1;
     }
     return SSDR_OK;

@@ -21,6 +21,7 @@
 #include "block_prims.hpp"
 #include "voxel_label.hpp"
 #include "subsample_types.hpp"
+#include "frontend.hpp"
 #include <map>
 #include <cstring>
 
@@ -537,20 +538,6 @@ int prune_device(const float* d_p, size_t n, float w, const uint8_t* d_rgb, cons
     SSDR_HIP(hipGetLastError());
     return SSDR_OK;
 }
-
-// frontend.hip: bucket partition + per-bucket LDS reduction (rows of at most 7 words, grids of at most 16384 buckets of 1024 voxels)
-bool frontend_fits(size_t fdim, size_t ldim);
-struct FePlan;          // a room plan: what the partition derives from the rooms' points and dl alone, kept between calls (frontend.hip)
-int frontend_batch_device(const float* d_p, const float* d_f, size_t fdim, const int32_t* d_c, size_t ldim, const int64_t* room_off, size_t nr, float dl,
-                          float* d_op, float* d_of, int32_t* d_oc, int64_t* d_om, GsParams* prm, hipStream_t s, const float* centres, size_t num_points, const FePlan* plan);
-int frontend_plan_build(const float* d_p, const float* d_f, size_t fdim, const int32_t* d_c, size_t ldim, const int64_t* room_off, size_t nr, float dl, hipStream_t s,
-                        FePlan** out);
-int frontend_plan_destroy(FePlan* plan);
-void frontend_plan_info(const FePlan* plan, int64_t* record_bytes, int32_t* sorted);
-int frontend_plan_check(const FePlan* plan, const float* d_p, const float* d_f, size_t fdim, const int32_t* d_c, size_t ldim, const int64_t* room_off, size_t nr, float dl);
-int frontend_tile_stats(hipStream_t s, int32_t* stage, int32_t* reduced, int32_t* buckets, size_t nr);
-void frontend_tile_forget(hipStream_t s);
-int frontend_scatter_stats(hipStream_t s, int64_t* scattered, int64_t* points, size_t nr);
 
 // centres (host [nr, 3]) / num_points: the partition path may leave out the buckets that cannot hold one of the num_points rows nearest to a room's centre
 // (ssdr_tile_from_rooms_batch_dev); NULL: every row of every cloud.  plan (optional): the partition path reads its tables instead of deriving them; the sort has no use for it

@@ -1,5 +1,5 @@
 """Worker of tests/test_subsample_paths.py::test_environment_selected_forms: a process of its own because the switches that select a form of the bucket
-partition (SSDR_FE_IMAGE, SSDR_FE_WGS, SSDR_FE_MOVE_WGS; csrc/frontend.hip) are static and read once per process.  Arguments: the library to bind (the gfx950
+partition (SSDR_FE_WGS, SSDR_FE_MOVE_WGS; csrc/frontend.hip) are static and read once per process.  Arguments: the library to bind (the gfx950
 build or the CPU logic build) and the group of inputs (tests/_fe_paths.py: form_inputs).  Every input goes through ssdr_grid_subsample_batch_dev under
 SSDR_SUBSAMPLE_AUTO and under SSDR_SUBSAMPLE_SORT, each printed as "CASE name rc status match": return code of ssdr_grid_subsample_status, its status word,
 and whether the rows of the clouds that must match equal the oracle's bit for bit.  The input conditions are asserted before the library is called."""

@@ -360,25 +360,11 @@ def many_items_clouds(crowded0, n1=60000, workgroups=2560):
 
 
 # ---- the environment-selected forms (tests/_fe_forms_worker.py runs a group, tests/test_subsample_paths.py asserts on every line) -----------
-FORM_ENV_NAMES = ("SSDR_FE_IMAGE", "SSDR_FE_WGS", "SSDR_FE_MOVE_WGS", "SSDR_FE_PADLDS", "SSDR_SUBSAMPLE_METHOD")
+FORM_ENV_NAMES = ("SSDR_FE_WGS", "SSDR_FE_MOVE_WGS", "SSDR_SUBSAMPLE_METHOD")
 
 
 def form_inputs(group):
     """-> [(name, clouds, dl, status AUTO must report, clouds whose rows AUTO must match)]; SORT must report 0 and match every cloud"""
-    if group == "image":
-        out = []
-        for fdim, ldim in ((3, 1), (1, 3), (0, 0)):
-            clouds, dl = layout_clouds(fdim, ldim)
-            out.append(("layout_%d_%d" % (fdim, ldim), clouds, dl, 0, (0, 1)))
-        for lab in ((0, 13), (-3, 20)):
-            clouds, dl = crowded_one_pass_clouds(lab)
-            out.append(("crowded_one_pass_lab%d" % lab[1], clouds, dl, 0, (0, 1)))
-            clouds, dl = crowded_sliced_clouds(lab)
-            out.append(("crowded_sliced_lab%d" % lab[1], clouds, dl, 0, (0,)))
-        cloud, need, dl = slice_limit_cloud(50000)
-        assert need <= FE_SLICES
-        out.append(("slices_below_limit", [cloud], dl, 0, (0,)))
-        return out
     assert group == "many"
     flagged, dl = many_items_clouds(True)
     healthy, _ = many_items_clouds(False)
@@ -387,9 +373,7 @@ def form_inputs(group):
 
 def form_names(group):
     """the lines the worker prints for a group, without building the inputs: name -> (status, match) expected"""
-    names = {"image": ["layout_3_1", "layout_1_3", "layout_0_0", "crowded_one_pass_lab13", "crowded_sliced_lab13", "crowded_one_pass_lab20", "crowded_sliced_lab20",
-                       "slices_below_limit"],
-             "many": ["many_items_flagged", "many_items"]}[group]
+    names = {"many": ["many_items_flagged", "many_items"]}[group]
     want = {}
     for nm in names:
         want[nm + "/auto"] = 4 if nm == "many_items_flagged" else 0

@@ -23,7 +23,7 @@ CEN3 = [(2.0, 1.5, 1.25), (11.5, -2.7, 2.0), (-4.0, 0.7, 0.5)]          # inside
 @pytest.fixture(autouse=True)
 def _default_switches(monkeypatch):
     """the switches are read at every plan creation: every case starts from the defaults"""
-    for k in ("SSDR_FE_PLAN_RECORDS", "SSDR_FE_PLAN_RECORDS_MAX_MB", "SSDR_FE_SCATTER_PRUNE", "SSDR_FE_IMAGE"):
+    for k in ("SSDR_FE_PLAN_RECORDS", "SSDR_FE_PLAN_RECORDS_MAX_MB"):
         monkeypatch.delenv(k, raising=False)
 
 

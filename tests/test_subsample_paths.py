@@ -17,8 +17,8 @@ not asserted there (the CPU build reports the key that does not fit beside the i
 Labels drawn uniformly from [0,13) leave every label of a 600- or 900-member voxel far below 256 members, and the fast vote's byte counters would be right
 without the exact vote; the crowded voxels of the [0,13) cases therefore give one label exactly 260 members (its byte shows 4: _fe_paths.wrapping_labels).
 
-Measured on one MI355X: `pytest -m gpu tests/test_subsample_paths.py` = 27 tests in 2.2 s (3.5 s wall with the interpreter's start), slowest the three child
-processes at 0.4 - 0.5 s each and the slice limit at 0.3 s.  The CPU logic build's leg (`-m "not gpu"`, 27 tests): 18 s on 8 threads.
+Measured on one MI355X: `pytest -m gpu tests/test_subsample_paths.py` = 26 tests in 1.3 s (2.6 s wall with the interpreter's start), slowest the child
+process at 0.5 s. The CPU logic build's leg (`-m "not gpu"`, 26 tests): 87 s on 8 threads.
 """
 import ctypes as C
 import os
@@ -57,14 +57,15 @@ def _check(orc, clouds, dl, auto=0, auto_match=None, sort=0, sort_match=None, ex
 
 
 # ---- 1. row layouts ---------------------------------------------------------------------------------------------------------------------------
-LAYOUTS = [(0, 0), (1, 0), (0, 1), (4, 0), (0, 4), (1, 3), (2, 2),      # the partition path's generic kernels: fe_scatter / fe_reduce / fe_move <-1, -1>
+LAYOUTS = [(3, 1),                                                      # the partition path's kernels for the hot path's rows: fe_scatter / fe_reduce / fe_move <3, 1>
+           (0, 0), (1, 0), (0, 1), (4, 0), (0, 4), (1, 3), (2, 2),      # its generic kernels: <-1, -1>
            (3, 2),                                                      # 8 words: the packed reduction of the sort at its full width
            (6, 2), (0, 6)]                                              # above 8 words: gs_reduce_b (+ gs_reduce_labels_b), features NULL in the second
 
 
 @pytest.mark.parametrize("fdim,ldim", LAYOUTS, ids=["f%d_l%d" % x for x in LAYOUTS])
 def test_row_layouts(backend, orc, fdim, ldim):
-    """Every row layout but (3, 1), NULL features / classes included, two clouds per call (one at negative coordinates)."""
+    """Every row layout, NULL features / classes included, two clouds per call (one at negative coordinates)."""
     clouds, dl = FP.layout_clouds(fdim, ldim)
     _check(orc, clouds, dl)
 
@@ -226,15 +227,12 @@ def test_state_reuse_on_a_callers_stream(backend, orc):
 
 
 # ---- 7. the environment-selected forms, one child process per environment ---------------------------------------------------------------------------
-FORM_ENVS = [("image", {"SSDR_FE_IMAGE": "1"}, "image"),
-             ("one_wg_per_cu", {"SSDR_FE_WGS": "1", "SSDR_FE_MOVE_WGS": "1"}, "many"),
-             ("image_one_wg_per_cu", {"SSDR_FE_IMAGE": "1", "SSDR_FE_WGS": "1", "SSDR_FE_MOVE_WGS": "1"}, "many")]
+FORM_ENVS = [("one_wg_per_cu", {"SSDR_FE_WGS": "1", "SSDR_FE_MOVE_WGS": "1"}, "many")]
 
 
 @pytest.mark.parametrize("name,env_add,group", FORM_ENVS, ids=[e[0] for e in FORM_ENVS])
 def test_environment_selected_forms(backend, name, env_add, group):
-    """SSDR_FE_IMAGE=1: fe_reduce<*, *, true> (records kept in LDS, rows over the bucket's own records) on the layouts, the crowded voxels and the sliced bucket.
-    SSDR_FE_WGS=1 SSDR_FE_MOVE_WGS=1: one workgroup per CU, so every workgroup of fe_reduce takes more than ten items one after another (and every wave of fe_move
+    """SSDR_FE_WGS=1 SSDR_FE_MOVE_WGS=1: one workgroup per CU, so every workgroup of fe_reduce takes more than ten items one after another (and every wave of fe_move
     several): the LDS state is reset between items, also behind an item that set L.bad.  The switches are read once per process: a child process each, never two at
     a time, no retry; every printed line is asserted."""
     from ssdr_al import _lib
