@@ -959,6 +959,27 @@ int ssdr_region_draw_dev(uint64_t seed, uint32_t round, uint32_t iteration, int 
 int ssdr_region_draw_shares(void* stream, int32_t* out, size_t n);
 int ssdr_seed_label_dev(const int32_t* d_gt, size_t n, const int32_t* d_sp_off, const int32_t* d_sp_pts, size_t S, const int32_t* d_items, const int32_t* d_n_items,
                         size_t max_items, size_t max_region, float* d_mask, float* d_label, uint8_t* d_labeled, int64_t* d_out, void* stream);
+/* The draw over a pool whose clouds lie on `world` ranks, contiguous shares in rank order: the union has a global cloud order and a global region id
+ * (first_region = the regions of the ranks before, + the local id), and a rank's share of every result is, index for index, ssdr_region_draw_dev over
+ * the union.  Two halves around ONE all-gather that the caller runs on the same stream:
+ *   ssdr_region_draw_count_dev: d_u int32 [cloud_slots + 1] <- this rank's unlabelled regions per cloud, zero at and behind num_clouds; the last word:
+ *     the rank's status bits (4: a region's cloud is outside the table).  cloud_slots: the largest cloud count of any rank, the same on all ranks.
+ *   the all-gather of d_u into d_u_all [world][cloud_slots + 1], rank-major.
+ *   ssdr_region_draw_sharded_dev: the live clouds, L, k, each_file_number, every cloud's take and first item over ALL ranks' clouds (global cloud =
+ *     rank * cloud_slots + cloud; replicated: total_num keys on every rank, as in one process), then the picks of this rank's own regions under their
+ *     cloud's global live rank and the word of g = first_region + region id.  d_items [max_items]: this rank's items as LOCAL ids, d_item_pos
+ *     [max_items] their positions in the union's list, ascending; *d_n_items of both are live.
+ *     d_info: [0] .. [4] the global values as above, [5] the OR of all ranks' status bits 1 and 4 and this rank's own bit 2, [6] this rank's items
+ *     (before the clamp to max_items), [7] zero.  ssdr_region_draw_shares afterwards: the global each_file_number.
+ * With world = 1 the two halves give ssdr_region_draw_dev's outputs.  Both only enqueue; refused before anything is launched, beyond the refusals above:
+ * world = 0, rank outside [0, world), cloud_slots < num_clouds (SSDR_ERR_INVALID); world * cloud_slots or first_region + S above 0x3fffffff
+ * (SSDR_ERR_UNSUPPORTED).  The scans sum the union's counts in 32 bits and a low rank cannot see the union's size: the caller, who sized the all-gather,
+ * keeps the regions of ALL ranks at or below 0x3fffffff.  A region whose cloud d_u_all counts as dead (tables of another mask) is not emitted. */
+int ssdr_region_draw_count_dev(const uint8_t* d_labeled, const int32_t* d_sp_cloud, size_t S, size_t num_clouds, int32_t* d_u, size_t cloud_slots, void* stream);
+int ssdr_region_draw_sharded_dev(uint64_t seed, uint32_t round, uint32_t iteration, int mode, int key_bits, uint64_t first_region, int rank, int world,
+                                 const int32_t* d_u_all, size_t cloud_slots, const uint8_t* d_labeled, const int32_t* d_sp_cloud, size_t S, size_t num_clouds,
+                                 size_t total_num, const int64_t* d_count, int32_t* d_items, int32_t* d_item_pos, size_t max_items, int32_t* d_n_items, int64_t* d_info,
+                                 void* stream);
 
 /* ---- the radix sort under every stage, alone (csrc/radix_sort.hip) ----
  * Stable sort of (u64 word, u32 value) pairs by bits [shift, shift + key_bits) of the word, 8 bits per pass, over nseg <= 64 independent segments of

@@ -176,6 +176,8 @@ def lib():
         L.ssdr_radix_sort_dev.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, vp]
         L.ssdr_radix_sort_info.argtypes = [vp, vp, vp]
         L.ssdr_region_draw_dev.argtypes = [u64, C.c_uint32, C.c_uint32, i32, i32, u64, vp, vp, sz, sz, sz, vp, vp, sz, vp, vp, vp]
+        L.ssdr_region_draw_count_dev.argtypes = [vp, vp, sz, sz, vp, sz, vp]
+        L.ssdr_region_draw_sharded_dev.argtypes = [u64, C.c_uint32, C.c_uint32, i32, i32, u64, i32, i32, vp, sz, vp, vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp]
         L.ssdr_region_draw_shares.argtypes = [vp, vp, sz]
         L.ssdr_seed_label_dev.argtypes = [vp, sz, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp]
         _lib = _libs[path] = L

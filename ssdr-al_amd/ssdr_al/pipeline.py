@@ -1118,9 +1118,14 @@ class HotPath:
         return self._label_end(out, d_cls, d_labeled, own[slots], pos[slots].astype(np.int64))
 
     # ---- the seed, random and label-all rounds (sampler2.py:344-520): no scoring, no network outputs ----------------
-    def _region_refuse_comm(self, comm):
-        if comm is not None:
-            raise ValueError('selector="%s" with a communicator: the sharded form of the seed / random / label-all samplers is not offered' % self.selector)
+    def _region_dist(self, comm):
+        """The tables of ONE sharded seed / random / label-all round, exchanged when it begins (nothing is kept between rounds: rooms, regions and labels may
+        all have changed): every rank's region, cloud and unlabelled count.  The ranks hold contiguous shares of the clouds in rank order, so the union has a
+        global region id (the regions of the ranks before + the local id) and every rank's count table takes the largest cloud count of any rank."""
+        sb = comm.allgather_host(np.array([self.S, self.B, int((~self.labeled_mask).sum())], np.int64))
+        S_all, CS = sb[:, 0], max(int(sb[:, 1].max()), 1)
+        return dict(S_all=S_all, first=int(S_all[: comm.rank].sum()), S_total=int(S_all.sum()), Smax=max(int(S_all.max()), 1), CS=CS, B_total=int(sb[:, 1].sum()),
+                    unl=int(sb[:, 2].sum()), d_u=DevArray((CS + 1,), np.int32), d_u_all=DevArray((comm.world, CS + 1), np.int32))
 
     def _unl_host(self):
         """draws="host": every cloud's unlabelled list (ids inside the cloud) as total_obj["unlabeled"] holds it; ascending when first made"""
@@ -1140,24 +1145,57 @@ class HotPath:
         draws="host" in the reference's own order, otherwise ascending"""
         return self._unl_host()
 
-    def _region_begin(self):
-        """the device state one seed / random / label-all round keeps across its iterations"""
+    def _region_begin(self, comm=None):
+        """the device state one seed / random / label-all round keeps across its iterations.  comm: a sharded round — R["unl"] is then the unlabelled
+        regions of ALL ranks, kept from replicated device words alone: every rank takes the loop's decisions from it, never from its own mask"""
         st = self.sel_stream
-        if self.S == 0:
-            raise ValueError("the seed / random / label-all samplers need at least one region")
+        _region_check_comm(self.selector, comm, self.draws)
+        D = None if comm is None else self._region_dist(comm)
+        if self.S == 0 or (D is not None and (D["S_all"] == 0).any()):      # (the exchanged counts: raised on every rank)
+            raise ValueError("the seed / random / label-all samplers need at least one region" + ("" if comm is None else " on every rank"))
+        if D is not None and D["S_total"] > 0x3fffffff:                     # (a low rank's own first_region + S does not show it)
+            raise ValueError("the sharded seed / random / label-all samplers take at most 0x3fffffff regions over all ranks (%d)" % D["S_total"])
         if self.pseudo_mask is None:
             self.set_pseudo_gt(np.zeros((2, self.n_pts), np.float32))
-        return dict(d_labeled=DevArray.from_host(self.labeled_mask.astype(np.uint8), st), d_items=DevArray((self.S,), np.int32), d_n=DevArray((1,), np.int32),
-                    d_info=DevArray((8,), np.int64), d_budget=DevArray((1,), np.int64), labeled=self.labeled_mask.copy(), it=0, drawn=[], infos=[], picks=None, items=None)
+        R = dict(d_labeled=DevArray.from_host(self.labeled_mask.astype(np.uint8), st), d_items=DevArray((self.S if D is None else D["Smax"],), np.int32),
+                 d_n=DevArray((1,), np.int32), d_info=DevArray((8,), np.int64), d_budget=DevArray((1,), np.int64), labeled=self.labeled_mask.copy(), it=0, drawn=[],
+                 infos=[], picks=None, items=None, comm=comm, positions=[], D=D)
+        if comm is not None:
+            R["d_pos"], R["unl"] = DevArray((D["Smax"],), np.int32), D["unl"]
+        return R
+
+    @staticmethod
+    def _region_all_labeled(R):
+        return R["labeled"].all() if R["comm"] is None else R["unl"] <= 0
 
     def _region_draw(self, R, click, mode, round_num):
         """One iteration's item list into R["d_items"] / R["d_n"]: `click` elements of range(total_num) shared among the live clouds, every cloud's picks
         (mode REGION_RANDOM), or every unlabelled region (REGION_ALL).  *R["d_budget"] holds `click`.  -> (items as global region ids, info)"""
-        L, st = _lib.lib(), self.sel_stream
-        T = self.S if self.total_num is None else self.total_num
+        L, st, comm = _lib.lib(), self.sel_stream, R["comm"]
+        T = self.total_num if self.total_num is not None else self.S if comm is None else R["D"]["S_total"]
         if mode == sampler.REGION_RANDOM and click > T:
             raise ValueError("Cannot take a larger sample than population when 'replace=False' (%d clicks of total_num = %d)" % (click, T))
-        if self.draws == "host":
+        if comm is not None:
+            # the draw in two halves around one all-gather of the ranks' count tables, all on the selection stream; every word the host decides on below is
+            # replicated.  items: this rank's, as local ids; info["pos"]: their places in the union's list
+            D = R["D"]
+            _lib.check(L.ssdr_region_draw_count_dev(R["d_labeled"].ptr, self.d_sp_cloud.ptr, self.S, max(self.B, 1), D["d_u"].ptr, D["CS"], st))
+            comm.allgather_(D["d_u"], D["d_u_all"], st)
+            _lib.check(L.ssdr_region_draw_sharded_dev(self.draw_seed & 0xffffffffffffffff, int(round_num) & 0xffffffff, R["it"], mode, self.draw_key_bits, D["first"], comm.rank,
+                                                      comm.world, D["d_u_all"].ptr, D["CS"], R["d_labeled"].ptr, self.d_sp_cloud.ptr, self.S, max(self.B, 1), T, R["d_budget"].ptr,
+                                                      R["d_items"].ptr, R["d_pos"].ptr, self.S, R["d_n"].ptr, R["d_info"].ptr, st))
+            w = R["d_info"].to_host(st)                           # waits for the selection stream alone
+            # (bit 2, the one word of d_info that is this rank's own, cannot be set: the item list holds S items; the raises below are from replicated bits)
+            sampler.region_draw_status_check(int(w[5]) & ~sampler.DRAW_ST_ITEMS, int(w[1]), T)
+            own = int(w[6])
+            items = R["d_items"].to_host(st)[:own].astype(np.int64)
+            info = dict(live=int(w[0]), k=int(w[1]), items=int(w[2]), remain=int(w[3]), each=None, own=own, pos=R["d_pos"].to_host(st)[:own].astype(np.int64),
+                        unlabeled=int(w[2] + w[4]))
+            if self.record_shares:
+                info["each"] = np.zeros(info["live"], np.int32)
+                _lib.check(L.ssdr_region_draw_shares(st, _lib.ptr(info["each"]), info["live"]))
+            R["positions"].append(info["pos"])
+        elif self.draws == "host":
             unl = self._unl_host()
             if mode == sampler.REGION_ALL:
                 picks, each, remain = [(c, list(unl[c])) for c in unl], np.array([len(unl[c]) for c in unl], np.int32), 0
@@ -1188,9 +1226,9 @@ class HotPath:
 
     def _region_select(self, comm=None):
         """step_selection() of "random" / "all": iteration 0's picks for the round's batch_size clicks — (arange, the picks as (cloud, region))"""
-        self._region_refuse_comm(comm)
-        R = self._region_begin()
-        R["click0"] = int(self._sel_static["batch"])
+        R = self._region_begin(comm)
+        # (a sharded round: sampling()'s batch_size is ONE number for all ranks, as _dist_setup has it)
+        R["click0"] = int(self._sel_static["batch"] if comm is None or self.batch_size is not None else self.select_per_tile * R["D"]["B_total"])
         self._region_set_budget(R, R["click0"])
         items, _ = self._region_draw(R, R["click0"], sampler.REGION_ALL if self.selector == "all" else sampler.REGION_RANDOM, self.round_num)
         self._drawn0, self._last_sel = R, None
@@ -1199,11 +1237,16 @@ class HotPath:
 
     def _region_label(self, mode, threshold, min_size, budget, comm):
         """label_selected() of "random" / "all": the walk over iteration 0's items, then (random) further draws and walks while clicks and unlabelled
-        regions last — RandomSampler._iteration's recursion (sampler2.py:463-493) as a loop that max_iter ends"""
-        self._region_refuse_comm(comm)
+        regions last — RandomSampler._iteration's recursion (sampler2.py:463-493) as a loop that max_iter ends.
+        comm: the communicator iteration 0 was drawn with.  One iteration's walk is then the sharded form (the items' places in the union's list as walk
+        keys -> verdict half -> all-gather of the records -> walk half on the iteration's d_labeled), and the loop is steered by the walk's replicated
+        d_out and the draw's replicated d_info alone: all ranks draw again, stop and raise together."""
+        _region_check_comm(self.selector, comm, self.draws)
         R = self._drawn0
         if R is None:
             raise RuntimeError("label_selected: no selection to label (run step_selection() first)")
+        if R["comm"] is not comm:
+            raise ValueError("label_selected: comm must be the communicator of the last selection (iteration 0 was drawn %s one)" % ("without" if R["comm"] is None else "with"))
         m = sampler.label_mode([mode] if isinstance(mode, str) else mode)
         if m == 1 and not self._pred_resident:
             raise ValueError('label_selected: mode="NAIL" with selector="%s" needs predicted classes resident from an earlier prediction pass (the reference '
@@ -1215,33 +1258,67 @@ class HotPath:
             R["click0"] = int(budget)                             # (label-all draws nothing: any budget walks the same list)
             self._region_set_budget(R, R["click0"])
         min_size = (self.min_size if min_size is None else int(min_size)) if rand else 1      # AllSampler passes min_size=1 (sampler2.py:449)
-        L, st, nc = _lib.lib(), self.sel_stream, int(self.cfg.num_classes)
-        max_region = int(self.sp_size_h.max()) if self.S else 1
         click, status = R["click0"], 0
-        counters, entries, used_ids, forms = np.zeros(6, np.int64), [], [], np.zeros(2, np.int64)
+        counters, entries, used_ids, forms, walk_pos = np.zeros(6, np.int64), [], [], np.zeros(2, np.int64), []
+        walk = self._region_walk if comm is None else self._region_walk_sharded
         while True:
-            items, M = R["items"], len(R["items"])
-            cap = max(1, min(M * nc, max(click, 0) + nc + 1))
-            d_used, d_proc = DevArray((max(M, 1),), np.uint8), DevArray((max(M, 1),), np.int32)
-            d_cls, d_out = DevArray((cap,), np.int32), DevArray((12,), np.int64)
-            _lib.check(L.ssdr_oracle_label_dev(self.tile_l.ptr, self.cls.ptr, self.n_pts, self.sp_off.ptr, self.sp_pts.ptr, self.S, self.d_sp_cloud.ptr, max(self.B, 1),
-                                               R["d_items"].ptr, R["d_n"].ptr, M, None, max_region, max(nc, 1), nc, m, float(threshold), min_size, R["d_budget"].ptr,
-                                               self.pseudo_mask.ptr, self.pseudo_label.ptr, d_used.ptr, R["d_labeled"].ptr, d_cls.ptr, cap, d_proc.ptr, d_out.ptr, st))
-            out = d_out.to_host(st)                              # the budget and the counters: one read per iteration
-            sampler.label_status_check(int(out[8]))
-            used_f, proc = d_used.to_host(st)[:M], d_proc.to_host(st)[:M]
-            used = items[proc[used_f[proc] != 0]] if M else items
+            out, ent, used, wpos = walk(R, click, m, float(threshold), min_size)
             self._region_spent(R, used)
-            counters += out[:6]; forms += out[10:12]; entries.append(d_cls.to_host(st)[: int(out[6])]); used_ids.append(used)
+            counters += out[:6]; forms += out[10:12]; entries.append(ent); used_ids.append(used); walk_pos.append(wpos)
             click = int(out[7])
             R["it"] += 1
-            if not rand or click <= 0 or R["labeled"].all():
+            if not rand or click <= 0 or self._region_all_labeled(R):
                 break
             if R["it"] >= self.max_iter:                         # only regions below min_size are left: the reference recurses for ever
                 status |= sampler.ST_MAX_ITER
                 break
             self._region_draw(R, click, sampler.REGION_RANDOM, self.round_num)
-        return self._region_end(R, counters, click, np.concatenate(used_ids), np.concatenate(entries), dict(wave=int(forms[0]), block=int(forms[1])), status)
+        return self._region_end(R, counters, click, np.concatenate(used_ids), np.concatenate(entries), dict(wave=int(forms[0]), block=int(forms[1])), status,
+                                walk_pos if comm is not None else None)
+
+    def _region_walk(self, R, click, m, threshold, min_size):
+        """the budget walk over one iteration's items -> (d_out, the new class entries, the used items in walk order, None)"""
+        L, st, nc = _lib.lib(), self.sel_stream, int(self.cfg.num_classes)
+        items, M = R["items"], len(R["items"])
+        cap = max(1, min(M * nc, max(click, 0) + nc + 1))
+        d_used, d_proc = DevArray((max(M, 1),), np.uint8), DevArray((max(M, 1),), np.int32)
+        d_cls, d_out = DevArray((cap,), np.int32), DevArray((12,), np.int64)
+        _lib.check(L.ssdr_oracle_label_dev(self.tile_l.ptr, self.cls.ptr, self.n_pts, self.sp_off.ptr, self.sp_pts.ptr, self.S, self.d_sp_cloud.ptr, max(self.B, 1),
+                                           R["d_items"].ptr, R["d_n"].ptr, M, None, int(self.sp_size_h.max()), max(nc, 1), nc, m, threshold, min_size, R["d_budget"].ptr,
+                                           self.pseudo_mask.ptr, self.pseudo_label.ptr, d_used.ptr, R["d_labeled"].ptr, d_cls.ptr, cap, d_proc.ptr, d_out.ptr, st))
+        out = d_out.to_host(st)                                  # the budget and the counters: one read per iteration
+        sampler.label_status_check(int(out[8]))
+        used_f, proc = d_used.to_host(st)[:M], d_proc.to_host(st)[:M]
+        return out, d_cls.to_host(st)[: int(out[6])], items[proc[used_f[proc] != 0]] if M else items, None
+
+    def _region_walk_sharded(self, R, click, m, threshold, min_size):
+        """the same walk over ALL ranks' items of one iteration: the items' places in the union's list as walk keys -> verdict half -> all-gather of the
+        records -> walk half on the iteration's d_labeled.  d_out is global and equal on every rank; it also gives R["unl"], the regions left unlabelled over
+        all ranks.  -> (d_out, the new class entries (global), this rank's used items in walk order, their walk positions)"""
+        L, st, nc, comm = _lib.lib(), self.sel_stream, int(self.cfg.num_classes), R["comm"]
+        D, W, items, n = R["D"], comm.world, R["items"], len(R["items"])
+        # the record slots per rank, one number on every rank: no rank holds more items than clicks are drawn for, or than the largest share has regions
+        M = max(1, D["Smax"] if self.selector == "all" else min(click, D["Smax"]))
+        keys = np.zeros(M, np.uint64); keys[:n] = R["info"]["pos"]
+        d_keys = DevArray.from_host(keys, st)
+        max_region = int(self.sp_size_h.max())
+        d_send, d_gath = DevArray((M * _lib.LABEL_RECORD_BYTES,), np.uint8), DevArray((W, M * _lib.LABEL_RECORD_BYTES), np.uint8)
+        _lib.check(L.ssdr_oracle_label_verdict_dev(self.tile_l.ptr, self.cls.ptr, self.n_pts, self.sp_off.ptr, self.sp_pts.ptr, self.S, R["d_items"].ptr, R["d_n"].ptr, M,
+                                                   d_keys.ptr, max_region, max(nc, 1), nc, m, threshold, min_size, d_send.ptr, st))
+        comm.allgather_(d_send, d_gath, st)
+        cap = max(1, min(W * M * nc, max(click, 0) + nc + 1))
+        d_used, d_wpos = DevArray((M,), np.uint8), DevArray((M,), np.int32)
+        d_cls, d_out = DevArray((cap,), np.int32), DevArray((12,), np.int64)
+        _lib.check(L.ssdr_oracle_label_walk_dev(d_gath.ptr, comm.rank, W, self.cls.ptr, self.n_pts, self.sp_off.ptr, self.sp_pts.ptr, self.S, R["d_items"].ptr, R["d_n"].ptr, M,
+                                                max_region, nc, R["d_budget"].ptr, self.pseudo_mask.ptr, self.pseudo_label.ptr, d_used.ptr, R["d_labeled"].ptr, d_cls.ptr, cap,
+                                                d_wpos.ptr, d_out.ptr, st))
+        out = d_out.to_host(st)
+        sampler.label_status_check(int(out[8]))
+        R["unl"] = R["info"]["unlabeled"] - int(out[9])          # (the draw's unlabelled regions less the items the walk used, both over all ranks)
+        used_f, wpos = d_used.to_host(st)[:n], d_wpos.to_host(st)[:n]
+        slots = np.flatnonzero(used_f != 0)
+        slots = slots[np.argsort(wpos[slots], kind="stable")]
+        return out, d_cls.to_host(st)[: int(out[6])], items[slots], wpos[slots].astype(np.int64)
 
     def _region_spent(self, R, used):
         """what _help / _help_seed do to the unlabelled lists once a walk has used `used` (global ids) of the iteration's items"""
@@ -1251,7 +1328,7 @@ class HotPath:
             for c, sps in R["picks"]:
                 sampler.remove_used(self._unl_lists, c, [s for s in sps if self.sp_base[c] + s in gone])
 
-    def _region_end(self, R, counters, budget_left, used_ids, entries, forms, status):
+    def _region_end(self, R, counters, budget_left, used_ids, entries, forms, status, walk_pos=None):
         st = self.sel_stream
         self._class_list_h = np.concatenate([self._class_list_h, entries]).astype(np.int32)
         self.selected_class_list = DevArray.from_host(self._class_list_h)
@@ -1262,19 +1339,22 @@ class HotPath:
         self.set_labeled({b: set(parts[b].tolist()) for b in range(self.B)})
         self._unl_lists = lists if self.draws == "host" else None      # (set_labeled drops them: these ARE the lists behind the new mask)
         return LabelResult(self, dict(zip(sampler.LABEL_COUNTERS, (int(x) for x in counters))), int(budget_left), _Pairs(*self._room_sp(np.asarray(used_ids, np.int64))),
-                           np.asarray(entries, np.int32), forms, None, iterations=R["it"], drawn=R["drawn"], status=status, draw_info=R["infos"])
+                           np.asarray(entries, np.int32), forms, walk_pos, iterations=R["it"], drawn=R["drawn"], status=status, draw_info=R["infos"],
+                           item_pos=R["positions"] if R["comm"] is not None else None)
 
-    def seed_round(self, number, round_num=0):
+    def seed_round(self, number, round_num=0, comm=None):
         """SeedSampler.sampling (sampler2.py:344-408): `number` regions drawn among the clouds and labelled PRECISELY (every point its own ground truth,
         no budget, no min_size, no class entries); a cloud smaller than its share is taken whole and the shortfall is drawn again, until none is left.
-        Returns a LabelResult: counters sp_num / p_num, budget_left = the remainder that could not be placed."""
+        Returns a LabelResult: counters sp_num / p_num, budget_left = the remainder that could not be placed.
+        comm: the clouds are sharded over the communicator's ranks; every rank labels its own items, the counters (summed on the selection stream), the
+        remainder and the iterations are those of all ranks."""
         L, st = _lib.lib(), self.sel_stream
-        R = self._region_begin()
+        R = self._region_begin(comm)
         remain, status = int(number), 0
         sp_num = p_num = 0
         max_region = int(self.sp_size_h.max()) if self.S else 1
         d_out = DevArray((3,), np.int64)
-        while remain > 0 and not R["labeled"].all():
+        while remain > 0 and not self._region_all_labeled(R):
             if R["it"] >= self.max_iter:
                 status |= sampler.ST_MAX_ITER
                 break
@@ -1282,8 +1362,11 @@ class HotPath:
             items, info = self._region_draw(R, remain, sampler.REGION_RANDOM, round_num)
             _lib.check(L.ssdr_seed_label_dev(self.tile_l.ptr, self.n_pts, self.sp_off.ptr, self.sp_pts.ptr, self.S, R["d_items"].ptr, R["d_n"].ptr, len(items), max_region,
                                              self.pseudo_mask.ptr, self.pseudo_label.ptr, R["d_labeled"].ptr, d_out.ptr, st))
+            if comm is not None:
+                comm.allreduce_sum_(d_out, st)                   # (a status bit of any rank stays non-zero in the sum)
+                R["unl"] = info["unlabeled"] - info["items"]
             out = d_out.to_host(st)
-            sampler.label_status_check(int(out[2]))
+            sampler.label_status_check(int(out[2]) if comm is None else 4 * int(out[2] != 0))
             sp_num += int(out[0]); p_num += int(out[1])
             self._region_spent(R, items)
             remain = info["remain"]
@@ -1309,6 +1392,16 @@ class HotPath:
         return out
 
 
+def _region_check_comm(selector, comm, draws):
+    """what the seed / random / label-all rounds ask of a communicator; raised before any exchange, so on every rank"""
+    if comm is None:
+        return
+    if not all(hasattr(comm, a) for a in ("rank", "world", "allgather_", "allgather_host", "allreduce_sum_")):
+        raise ValueError('selector="%s": comm = %r is not a communicator (ssdr_al.distributed.Comm)' % (selector, comm))
+    if draws == "host":
+        raise ValueError('draws="host" with a communicator: the RandomState chain is sequential over all clouds\' lists, which no rank holds; use draws="device"')
+
+
 def _new_stream():
     st = C.c_void_p()
     _lib.check(_lib.lib().ssdr_stream_create(C.byref(st)))
@@ -1321,14 +1414,18 @@ class LabelResult:
     reference's `w`, `budget_left` (may be negative), `class_entries` appended to selected_class_list, `forms`: regions judged per kernel form,
     `walk_pos`: the position of every entry of `used` in the walk, `iterations` / `drawn` / `status`: the draw iterations of a seed, random or
     label-all round, their items and why the loop stopped (budget_left is the seed round's remainder).  After a sharded labelling the counters, budget_left, class_entries and forms are
-    global (equal on all ranks), `used` / `walk_pos` this rank's share of the global walk."""
-    def __init__(self, hp, counters, budget_left, used, class_entries, forms, walk_pos=None, iterations=1, drawn=None, status=0, draw_info=None):
+    global (equal on all ranks), `used` / `walk_pos` this rank's share of the global walk.  After a sharded seed, random or label-all round `drawn` are this
+    rank's items per iteration, `item_pos` their positions in the union's item list and `walk_pos` the used regions' walk positions per iteration (lists
+    of arrays); `iterations`, `status` and `draw_info` (k, live clouds, items, remainder, `each`) are global too."""
+    def __init__(self, hp, counters, budget_left, used, class_entries, forms, walk_pos=None, iterations=1, drawn=None, status=0, draw_info=None, item_pos=None):
         self._hp, self.mask, self.label = hp, hp.pseudo_mask, hp.pseudo_label
         self.counters, self.budget_left, self._used, self.class_entries, self.forms = counters, budget_left, used, class_entries, forms
         self.walk_pos = walk_pos
         # the seed / random / label-all rounds: iterations run, the items of every iteration (region ids), sampler.ST_MAX_ITER when max_iter stopped the loop
         # draw_info: per iteration dict(live, k, items, remain, each) — the live clouds, the clicks drawn for, the items, the seed remainder, each_file_number
-        self.iterations, self.drawn, self.status, self.draw_info = int(iterations), drawn, int(status), draw_info
+        # sharded: `drawn` are this rank's items per iteration (local region ids), `item_pos` their places in the union's item list, `walk_pos` the used
+        # regions' walk positions, both per iteration: enough to merge the ranks' results into the single process's order; the rest is global
+        self.iterations, self.drawn, self.status, self.draw_info, self.item_pos = int(iterations), drawn, int(status), draw_info, item_pos
 
     @property
     def used(self):
@@ -1386,7 +1483,7 @@ class ALRound:
             if selector == "coregcn":
                 raise ValueError('selector="coregcn" with a communicator: the sharded form of the trained-GCN selector is not offered')
             if selector in REGION_SAMPLERS:
-                raise ValueError('selector="%s" with a communicator: the sharded form of the seed / random / label-all samplers is not offered' % selector)
+                _region_check_comm(selector, comm, draws)
             if comm.world > int(n_batches):                   # (raised on every rank: nobody is left waiting in an exchange)
                 raise ValueError("ALRound: %d batches cannot be shared among %d ranks (a rank would own none)" % (int(n_batches), comm.world))
             self.batch_ids = [int(b) for b in np.array_split(np.arange(int(n_batches)), comm.world)[comm.rank]]
@@ -1510,10 +1607,9 @@ class ALRound:
         return self.sel.label_selected(mode=mode, threshold=threshold, min_size=min_size, budget=budget, comm=self.comm)
 
     def seed(self, number, round_num=0):
-        """SeedSampler over the round's regions (HotPath.seed_round): the labelled set every experiment starts from, in place of the labelled stand-in"""
-        if self.comm is not None:
-            raise ValueError("ALRound.seed with a communicator: the sharded form of the seed / random / label-all samplers is not offered")
-        return self.sel.seed_round(number, round_num)
+        """SeedSampler over the round's regions (HotPath.seed_round): the labelled set every experiment starts from, in place of the labelled stand-in;
+        a sharded round seeds over all ranks' regions with its communicator"""
+        return self.sel.seed_round(number, round_num, comm=self.comm)
 
 
 class BatchStreams:

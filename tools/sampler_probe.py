@@ -6,7 +6,11 @@ NumPy restatement of the same rule (tests/_sampler_oracle.py: no pickles, no PLY
 Both start from the same labelled mask every time; the two results are compared once.  Median of --repeats after a warm-up, ms.  The launches per
 iteration are counted from the code (csrc/select_random.hip, csrc/select_label.hip, RadixSorter::sort_segments) for the pool's sizes.
 
-Prints one JSON line.  GPU only.  Usage: python tools/sampler_probe.py [--clouds 272] [--regions 100000] [--clicks 10000] [--repeats 3]"""
+--comm: the same round through the SHARDED form at world 1 (RCCL: ssdr_region_draw_count_dev -> all-gather -> ssdr_region_draw_sharded_dev, the walk in
+its verdict / all-gather / walk halves) against the plain path, in one call, alternating, median of --repeats after a warm-up; also written to
+profiles/sampler_probe_comm.json.  No multi-GPU figure: what it shows is what the two exchanges and the split chains cost where nothing is exchanged.
+
+Prints one JSON line.  GPU only.  Usage: python tools/sampler_probe.py [--clouds 272] [--regions 100000] [--clicks 10000] [--repeats 3] [--comm]"""
 import argparse
 import json
 import os
@@ -44,13 +48,51 @@ def sort_launches(key_bits, n, wide_high):
     return 2 + 3 * (allp if wide else min(4, allp)) + (1 if key_bits > 32 and not wide else 0) + 1
 
 
+def comm_probe(a, hp, device_round, sort_launches):
+    """the plain round and the sharded round at world 1, alternating"""
+    import torch.distributed as dist
+    from ssdr_al.distributed import Comm
+    comm = Comm(dist, "cuda")
+    device_round(); device_round(comm)                       # warm-up: scratch, code objects, the communicator's first collective
+    t_plain, t_comm = [], []
+    for _ in range(a.repeats):
+        ms, plain = device_round(); t_plain.append(ms)
+        ms, shard = device_round(comm); t_comm.append(ms)
+    same = (plain.iterations == shard.iterations and all(np.array_equal(x, y) for x, y in zip(plain.drawn, shard.drawn)) and plain.used == shard.used
+            and plain.counters == shard.counters and plain.budget_left == shard.budget_left and np.array_equal(plain.to_host(), shard.to_host()))
+    rank_bits = 1
+    while (1 << rank_bits) <= hp.B:
+        rank_bits += 1
+    # draw: count half (fill, count), the all-gather, sharded half (fill, live, keys, sort, share, take, pick keys, sort, emit); walk: the keys' upload, verdict half
+    # (two fills, ident, two verdict forms, pack), the all-gather, walk half (three fills, record keys, the 64-bit sort, scan, two apply forms)
+    draw = 2 + 7 + sort_launches(32, hp.S, False) + sort_launches(32 + rank_bits, hp.S, True)
+    walk = 6 + 6 + sort_launches(64, a.clicks, True)
+    med = lambda v: round(float(np.median(v)), 2)
+    out = dict(probe="sampler_comm", world=1, backend="rccl", clouds=hp.B, regions=hp.S, clicks=a.clicks, iterations=shard.iterations,
+               items_per_iteration=[len(x) for x in shard.drawn], plain_round_ms=dict(median=med(t_plain), best=round(min(t_plain), 2), all=[round(x, 2) for x in t_plain]),
+               sharded_round_ms=dict(median=med(t_comm), best=round(min(t_comm), 2), all=[round(x, 2) for x in t_comm]),
+               launches_per_iteration=dict(draw=draw, walk=walk, collectives=2, host_uploads=1), sharded_equals_plain=bool(same))
+    with open(os.path.join(ROOT, "profiles", "sampler_probe_comm.json"), "w") as f:
+        json.dump(out, f, indent=1); f.write("\n")
+    print(json.dumps(out))
+    dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clouds", type=int, default=272)
     ap.add_argument("--regions", type=int, default=100000)
     ap.add_argument("--clicks", type=int, default=10000)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--comm", action="store_true", help="time the sharded form at world 1 (RCCL) against the plain path")
     a = ap.parse_args()
+    if a.comm:                                               # the framework takes the device first: one HIP runtime per process
+        import torch
+        import torch.distributed as dist
+        for k, v in (("MASTER_ADDR", "127.0.0.1"), ("MASTER_PORT", "29593"), ("RANK", "0"), ("WORLD_SIZE", "1")):
+            os.environ.setdefault(k, v)
+        torch.cuda.set_device(0)
+        dist.init_process_group("nccl", device_id=torch.device("cuda", 0))
     import _sampler_oracle as SO
     from ssdr_al import _lib, pipeline
     from ssdr_al.helper_tool import ConfigS3DIS
@@ -64,13 +106,13 @@ def main():
     base = np.concatenate([np.asarray(hp.sp_base, np.int64), [hp.S]])
     n_pts = hp.n_pts
 
-    def device_round():
+    def device_round(comm=None):
         hp.set_labeled({b: set() for b in range(hp.B)})
         hp.set_pseudo_gt(np.zeros((2, n_pts), np.float32))
         _lib.sync()
         c0 = time.perf_counter()
-        hp.step_selection()
-        res = hp.label_selected(mode="dominant")
+        hp.step_selection(comm)
+        res = hp.label_selected(mode="dominant", comm=comm)
         return 1e3 * (time.perf_counter() - c0), res
 
     def numpy_round():
@@ -80,6 +122,8 @@ def main():
         exp = SO.random_round(seed, rnd, clouds, lab, base, pseudo, a.clicks, min_size)
         return 1e3 * (time.perf_counter() - c0), exp, pseudo
 
+    if a.comm:
+        return comm_probe(a, hp, device_round, sort_launches)
     device_round()                                           # warm-up: scratch, code objects
     t_dev, t_np = [], []
     for _ in range(a.repeats):
